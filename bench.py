@@ -15,9 +15,19 @@ same `--batch` queries per step; one "lookup" = one query fully resolved
 against the whole corpus.
 
 Launch (driver contract):
-  python bench.py --gpus 1 --steps 20 --warmup 5
+  python bench.py --gpus 1 --steps 20 --warmup 5 [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 \
       --master-addr 127.0.0.1 bench.py --gpus 8 --steps 20 --warmup 5
+
+A plain run does only what the headline figure needs: set up, warm up, time
+`--steps` steps, print one JSON line. `--dump-outputs DIR` additionally
+writes what the last timed step returned to its caller (rank 0 only) as
+DIR/scores.npy (f32 [batch, topk]), DIR/ids.npy (global ids as f64, exact
+below 2^53) and DIR/warn_count.npy (f64 [1]); inputs are seeded, so two
+builds run with the same arguments can be compared output for output.
+`--full` is where any measurement beyond the headline figure belongs (CPU
+baselines, other sizes or precisions, per-kernel figures); the benchmark has
+none today, so the flag currently adds nothing to a plain run.
 """
 
 from __future__ import annotations
@@ -42,6 +52,17 @@ def parse_args():
     p.add_argument("--topk", type=int, default=5)
     p.add_argument("--dim", type=int, default=768)
     p.add_argument("--threshold", type=float, default=0.8)
+    p.add_argument(
+        "--dump-outputs",
+        metavar="DIR",
+        default=None,
+        help="write the last timed step's outputs to DIR/<name>.npy",
+    )
+    p.add_argument(
+        "--full",
+        action="store_true",
+        help="also run measurements beyond the headline figure (none today)",
+    )
     return p.parse_args()
 
 
@@ -105,6 +126,8 @@ def main():
     feat_idx = torch.from_numpy(idx_np).to(device).repeat(reps, 1)[:B].contiguous()
     feat_w = torch.from_numpy(w_np).to(device).repeat(reps, 1)[:B].contiguous()
 
+    last = {}
+
     def step() -> int:
         # 1. encode on GPU (embedding_bag kernel + projection GEMM + norm)
         q = enc.encode_features(feat_idx, feat_w).to(cdtype)
@@ -113,7 +136,7 @@ def main():
         fs, fid = store.search(q, k)
         # 5. threshold policy decision
         warn = (fs[:, 0] >= args.threshold).sum()
-        _ = fid
+        last["scores"], last["ids"], last["warn_count"] = fs, fid, warn
         return int(warn.item() >= 0)
 
     # ---- warmup ----------------------------------------------------------
@@ -153,6 +176,20 @@ def main():
     lookups_per_sec = B * args.steps / elapsed
     ms_per_step = elapsed / args.steps * 1000.0
     p50_ms = statistics.median(times) * 1000.0
+
+    if rank == 0 and args.dump_outputs and last:
+        import numpy as np
+
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, t, dt in (
+            ("scores", last["scores"], torch.float32),
+            ("ids", last["ids"], torch.float64),
+            ("warn_count", last["warn_count"].reshape(1), torch.float64),
+        ):
+            np.save(
+                os.path.join(args.dump_outputs, name + ".npy"),
+                t.detach().to("cpu", dt).numpy(),
+            )
 
     if rank == 0:
         out = {

@@ -12,9 +12,15 @@ import sys
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _run(cmd, timeout=240):
+def _run(cmd, timeout=240, hide_gpus=False):
+    env = dict(os.environ)
+    if hide_gpus:
+        # an out-of-range ordinal leaves the HIP runtime with no visible
+        # device, so the child takes the CPU dry-run path on a GPU host too
+        env["HIP_VISIBLE_DEVICES"] = "-1"
+        env["CUDA_VISIBLE_DEVICES"] = "-1"
     return subprocess.run(
-        cmd, cwd=REPO, capture_output=True, text=True, timeout=timeout
+        cmd, cwd=REPO, capture_output=True, text=True, timeout=timeout, env=env
     )
 
 
@@ -57,10 +63,36 @@ def test_bench_single_process_cpu_dryrun():
     _check_contract(_last_json(r.stdout), n_gpus=1, steps=2, warmup=1)
 
 
+def test_bench_dump_outputs_reproducible(tmp_path):
+    """--dump-outputs writes the last timed step's outputs as float
+    .npy files, identical from run to run for the same arguments
+    (seeded inputs); --full is accepted and keeps the result line."""
+    import numpy as np
+
+    base = [sys.executable, "bench.py", "--steps", "2", "--warmup", "1",
+            "--entries", "20000", "--batch", "64"]
+    dumps = []
+    for name, extra in (("a", []), ("b", ["--full"])):
+        d = tmp_path / name
+        r = _run(base + ["--dump-outputs", str(d)] + extra)
+        assert r.returncode == 0, r.stderr[-2000:]
+        _check_contract(_last_json(r.stdout), n_gpus=1, steps=2, warmup=1)
+        dumps.append({p.name: np.load(p) for p in sorted(d.glob("*.npy"))})
+    a, b = dumps
+    assert set(a) == {"scores.npy", "ids.npy", "warn_count.npy"}
+    assert a["scores.npy"].shape == (64, 5) and a["scores.npy"].dtype == np.float32
+    assert a["ids.npy"].shape == (64, 5) and a["ids.npy"].dtype == np.float64
+    assert (a["ids.npy"] >= 0).all() and (a["ids.npy"] < 20000).all()
+    for name in a:
+        assert np.array_equal(a[name], b[name]), name
+
+
 def test_bench_torchrun_world2_cpu_dryrun():
     """The exact driver launch: torch.distributed.run, nproc 2, master
     127.0.0.1. On CPU this uses gloo + the same ShardedStore all-gather
-    merge the RCCL path uses."""
+    merge the RCCL path uses. A world of 2 needs 2 devices, so on a GPU
+    host the GPUs are hidden from the children: this is the CPU dry run
+    wherever it runs."""
     r = _run(
         [
             sys.executable,
@@ -86,6 +118,7 @@ def test_bench_torchrun_world2_cpu_dryrun():
             "64",
         ],
         timeout=300,
+        hide_gpus=True,
     )
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-1500:])
     out = _last_json(r.stdout)

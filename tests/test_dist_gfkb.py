@@ -10,6 +10,14 @@ import torch.multiprocessing as mp
 WORLD = 2
 
 
+def _hide_gpus(monkeypatch):
+    """These are CPU/gloo tests: the coordinator picks cuda:LOCAL_RANK when
+    it sees a GPU, and a world of 2 does not fit a single-GPU host. An
+    out-of-range ordinal leaves the spawned ranks with no visible device."""
+    monkeypatch.setenv("HIP_VISIBLE_DEVICES", "-1")
+    monkeypatch.setenv("CUDA_VISIBLE_DEVICES", "-1")
+
+
 def _worker(rank: int, world: int, port: int, q):
     os.environ.update(
         MASTER_ADDR="127.0.0.1",
@@ -61,7 +69,8 @@ def _worker(rank: int, world: int, port: int, q):
         td.destroy_process_group()
 
 
-def test_dist_gfkb_service_roundtrip():
+def test_dist_gfkb_service_roundtrip(monkeypatch):
+    _hide_gpus(monkeypatch)
     ctx = mp.get_context("spawn")
     q = ctx.SimpleQueue()
     procs = [
@@ -141,7 +150,8 @@ def _engine_worker(rank: int, world: int, port: int, q):
         td.destroy_process_group()
 
 
-def test_dist_gfkb_engine_over_coordinator():
+def test_dist_gfkb_engine_over_coordinator(monkeypatch):
+    _hide_gpus(monkeypatch)
     ctx = mp.get_context("spawn")
     q = ctx.SimpleQueue()
     procs = [
