@@ -14,360 +14,243 @@ static void check_bf16_2d(const torch::Tensor& t, const char* name) {
   TORCH_CHECK(t.dim() == 2 && t.is_contiguous(), name, " must be contiguous 2-D");
 }
 
-std::tuple<torch::Tensor, torch::Tensor> cosine_topk(
-    torch::Tensor queries, torch::Tensor corpus, int64_t k, int64_t valid_n) {
-  check_bf16_2d(queries, "queries");
-  check_bf16_2d(corpus, "corpus");
-  const int B = queries.size(0);
-  const int D = queries.size(1);
-  const int N = (int)valid_n;
-  TORCH_CHECK(corpus.size(1) == D, "dim mismatch");
-  TORCH_CHECK(N >= 1 && N <= corpus.size(0), "valid_n out of range");
-  TORCH_CHECK(D % BK == 0, "D must be a multiple of ", BK);
-  TORCH_CHECK(k >= 1 && k <= KMAX, "k must be in [1,", KMAX, "]");
+namespace {
 
-  // kernel selection. Default: the 128x128 2-blocks/CU kernel (fastest
-  // END-TO-END: its epilogue hides under the sibling block's MFMAs).
-  // KAKVEDA_KNN_KERNEL=8p/8pbl/8pq opt into the experimental 256x256
-  // 8-phase pipeline (stash / ballot-skip / queue epilogue; all exact,
-  // GPU-suite-covered) whose GEMM core measures ~1.0 PF but whose
-  // epilogue is still partially exposed at 1 block/CU — the remaining
-  // round-2 item (ROUND2.md).
-  static const char* ksel = std::getenv("KAKVEDA_KNN_KERNEL");
-  // emission-epilogue re-entry guard: an overflowed emission run falls
-  // back to the list-epilogue path exactly once
-  static thread_local int emit_fallback = 0;
-  const bool use8pbl = (ksel && std::string(ksel) == "8pbl") && N >= 4096;
-  const bool use8pq = (ksel && std::string(ksel) == "8pq") && N >= 4096;
-  // 8pe: the 8-phase GEMM core with the threshold-emission epilogue +
-  // emit_merge_topk (no in-kernel lists). Needs the prepass floors, so
-  // only for corpora big enough to carry one (>= 64k columns).
-  // DEFAULT for every N >= 64k with k > 1 since the stash-drain cold
-  // path went spill-free: same-box A/B measured +26% at 1M, +22% at 2M,
-  // parity at 6M and +4.5% at 10M over the ballot kernel
-  // (profiles/knn_kernel_history.md round 2). Any explicit
-  // KAKVEDA_KNN_KERNEL selection other than 8pe disables it.
-  const bool use8pv3 = (ksel && std::string(ksel) == "8pv3") && N >= 65536 &&
-                       !emit_fallback;  // isolation A/B: v3 cold path
-  // 8pe2 (EPI_MODE 15): emission epilogue with block-lifetime threshold
-  // vectors — the per-tile hot sweep drops its 32 ds_bpermute + 32
-  // ballots for a pure-VALU running max + one ballot (kernels_impl.h)
-  const bool use8pv2 = (ksel && std::string(ksel) == "8pe2") && N >= 65536 &&
-                       !emit_fallback;
-  const bool use8pe =
-      ((ksel ? std::string(ksel) == "8pe" : k > 1) || use8pv3 || use8pv2) &&
-      N >= 65536 && !emit_fallback;
-  // B <= 8 requests (single-query serving) skip the MFMA tile machinery
-  // entirely: the streaming smallb_emit_kernel reads the corpus once at
-  // full bandwidth with the same emission floors/merge
-  const bool use_smallb = use8pe && B <= 8;
-  const bool use8p =
-      ((ksel && std::string(ksel) == "8p") || use8pbl || use8pq || use8pe) &&
-      N >= 4096;
-  // Epilogue selection: default is EPI_MODE 11 (register-cached per-row
-  // thresholds + ballot pre-check + inline single-insert fast path with
-  // noinline fallback — measured fastest within-probe: 745 vs 642 TF
-  // for EPI_MODE 0 at B=4096 x N=2M). KAKVEDA_KNN_KERNEL=eager -> 0
-  // (volatile-LDS thresholds), =rege -> 8 (register thresholds,
-  // call-only extraction), =fast -> 9 (shfl-reduce pre-check), =dfr ->
-  // 7 (deferred extraction; measured slower, kept for reference).
-  const int epi = ksel ? (std::string(ksel) == "dfr"     ? 7
-                          : std::string(ksel) == "eager" ? 0
-                          : std::string(ksel) == "rege"  ? 8
-                          : std::string(ksel) == "fast"  ? 9
-                                                         : 11)
-                       : 11;
+// The operands every search kernel takes.
+struct KnnArgs {
+  const bf16_t* q;
+  const bf16_t* c;
+  int B, N, D;
+  hipStream_t stream;
+  torch::Device dev;
+  torch::TensorOptions f32() const { return torch::TensorOptions().dtype(torch::kFloat32).device(dev); }
+  torch::TensorOptions i32() const { return torch::TensorOptions().dtype(torch::kInt32).device(dev); }
+  torch::TensorOptions i64() const { return torch::TensorOptions().dtype(torch::kInt64).device(dev); }
+};
 
-  const int tile_m = use8p ? BM8 : BM;
-  const int tile_n = use8p ? BN8 : BN;
-  const int row_tiles = (B + tile_m - 1) / tile_m;
-  const int ntiles = (N + tile_n - 1) / tile_n;
-  // size chunks so the grid comfortably oversubscribes 256 CUs
-  // (KAKVEDA_KNN_TARGET overrides the target block count for tuning)
-  static const char* tenv = std::getenv("KAKVEDA_KNN_TARGET");
-  static const long tover = tenv ? std::atol(tenv) : 0;
-  const long target = tover > 0 ? tover : (use8p ? 512 : 2048);
-  long want = ((long)ntiles * row_tiles + target - 1) / target;
-  const int chunk_tiles = (int)std::max(4L, std::min(want, 128L));
-  // pad the chunk count to a multiple of 8 so the in-kernel XCD remap is
-  // bijective; padded chunks have no tiles and emit -inf partials.
-  const int nchunks = ((ntiles + chunk_tiles - 1) / chunk_tiles + 7) & ~7;
+KnnArgs knn_args(const torch::Tensor& queries, const torch::Tensor& corpus, int N) {
+  return {(const bf16_t*)queries.data_ptr(), (const bf16_t*)corpus.data_ptr(),
+          (int)queries.size(0), N, (int)queries.size(1),
+          c10::hip::getCurrentHIPStream().stream(), queries.device()};
+}
 
-  auto opts_f = torch::TensorOptions().dtype(torch::kFloat32).device(queries.device());
-  auto opts_i = torch::TensorOptions().dtype(torch::kInt32).device(queries.device());
-  auto pscore = torch::empty({(long)B * nchunks * KMAX}, opts_f);
-  auto rowthr = torch::empty({B}, opts_i);
-  auto pidx = torch::empty({(long)B * nchunks * KMAX}, opts_i);
-  auto out_score = torch::empty({B, k}, opts_f);
-  auto out_idx = torch::empty({B, k}, torch::TensorOptions().dtype(torch::kInt64).device(queries.device()));
-
-  auto stream = c10::hip::getCurrentHIPStream();
-  dim3 grid(nchunks, row_tiles);
-  hipLaunchKernelGGL(init_rowthr, dim3((B + 255) / 256), dim3(256), 0,
-                     stream.stream(), (unsigned*)rowthr.data_ptr<int>(), B);
-  // (the EPI_MODE 5 score slab is probe-only; no host path passes it, so
-  // nothing allocates the ~650 MB/call buffer anymore)
-  // Threshold pre-pass: one cheap launch over the first PRE_TILES*PREG
-  // column tiles fills each row's lists from a ~4k-column sample and
-  // publishes their minima into rowthr, so the main launch's blocks all
-  // start with near-converged pruning thresholds instead of each paying
-  // the bootstrap insert storm (measured: warm thresholds are worth
-  // ~10% end-to-end; the sample scan is ~0.5% extra work, its partial
-  // writes land in slots the main launch overwrites).
-  // grid.x must stay < nchunks so every pre-pass block's partial slot
-  // [row][chunk_id] is in bounds (the main launch overwrites them all)
-  static const char* pgenv = std::getenv("KAKVEDA_KNN_PREG");
-  static const int preg_want = pgenv ? (int)std::atol(pgenv) : 0;
-  // emission floors tighten with sample size (E[emitted/row] ~ 8N/sample):
-  // default to a 4x bigger prepass for the emission path at large N
-  const int preg_base = use8pe ? 256 : 64;
-  const int preg =
-      std::min(preg_want > 0 ? preg_want : preg_base, nchunks) & ~7;
-  constexpr int PRE_TILES = 8;
-  // Pay the pre-pass only when the sample is a meaningful fraction of
-  // the corpus (>= ~3%): below that its published floor is weaker than
-  // what the main launch's own publishes converge to almost immediately
-  // (measured: +14% at 1M entries, noise-negative at 10M).
-  // KAKVEDA_KNN_PREPASS=0/1 forces it off/on.
-  static const char* penv = std::getenv("KAKVEDA_KNN_PREPASS");
-  const bool psmall = ntiles <= preg * PRE_TILES * 32;
-  // the emission path REQUIRES the prepass: its published list minima are
-  // the exact per-row emission thresholds (see kernels_impl.h EPI_MODE 9)
-  const bool prepass = (use8pe || (!use8p && k > 1 &&
-                                   ntiles >= preg * PRE_TILES &&
-                                   (penv ? penv[0] == '1' : psmall))) &&
-                       preg >= 8;
-  // emission path: the prepass writes a COMPACT [B][preg][KMAX] partial
-  // buffer of its own (stride preg), so the floor merge scans only what
-  // the prepass produced instead of the whole [B][nchunks] layout
-  torch::Tensor ppre_s, ppre_i;
-  if (use8pe && prepass) {
-    ppre_s = torch::empty({(long)B * preg * KMAX}, opts_f);
-    ppre_i = torch::empty({(long)B * preg * KMAX}, opts_i);
+// ---- one launch site per kernel template ---------------------------------
+using Partial128Fn = decltype(&cosine_topk_partial_t<11>);
+Partial128Fn partial128_kernel(int mode) {
+  switch (mode) {
+    case 0: return cosine_topk_partial_t<0>;
+    case 4: return cosine_topk_partial_t<4>;
+    case 8: return cosine_topk_partial_t<8>;
+    case 9: return cosine_topk_partial_t<9>;
+    case 11: return cosine_topk_partial_t<11>;
   }
-  if (prepass) {
-    float* const pre_s =
-        use8pe ? ppre_s.data_ptr<float>() : pscore.data_ptr<float>();
-    int* const pre_i = use8pe ? ppre_i.data_ptr<int>() : pidx.data_ptr<int>();
-    const int pre_stride = use8pe ? preg : nchunks;
-    // the prepass always runs the 128-row-tile kernel, also under the
-    // 256-row-tile 8p main launch
-    dim3 pgrid(preg, (B + BM - 1) / BM);
-    if (epi == 11)
-      hipLaunchKernelGGL((cosine_topk_partial_t<11>), pgrid, dim3(THREADS), 0, stream.stream(),
-                         (const bf16_t*)queries.data_ptr(), (const bf16_t*)corpus.data_ptr(),
-                         pre_s, pre_i,
-                         B, N, D, PRE_TILES, pre_stride,
-                         (unsigned*)rowthr.data_ptr<int>(), (unsigned long long*)nullptr);
-    else if (epi == 7)
-      hipLaunchKernelGGL((cosine_topk_partial_t<7>), pgrid, dim3(THREADS), 0, stream.stream(),
-                         (const bf16_t*)queries.data_ptr(), (const bf16_t*)corpus.data_ptr(),
-                         pre_s, pre_i,
-                         B, N, D, PRE_TILES, pre_stride,
-                         (unsigned*)rowthr.data_ptr<int>(), (unsigned long long*)nullptr);
-    else if (epi == 0)
-      hipLaunchKernelGGL((cosine_topk_partial_t<0>), pgrid, dim3(THREADS), 0, stream.stream(),
-                         (const bf16_t*)queries.data_ptr(), (const bf16_t*)corpus.data_ptr(),
-                         pre_s, pre_i,
-                         B, N, D, PRE_TILES, pre_stride,
-                         (unsigned*)rowthr.data_ptr<int>(), (unsigned long long*)nullptr);
-    else
-      hipLaunchKernelGGL((cosine_topk_partial_t<8>), pgrid, dim3(THREADS), 0, stream.stream(),
-                         (const bf16_t*)queries.data_ptr(), (const bf16_t*)corpus.data_ptr(),
-                         pre_s, pre_i,
-                         B, N, D, PRE_TILES, pre_stride,
-                         (unsigned*)rowthr.data_ptr<int>(), (unsigned long long*)nullptr);
+  TORCH_CHECK(false, "no 128x128 kernel for EPI_MODE ", mode);
+}
+
+void launch_partial128(int mode, dim3 grid, const KnnArgs& a, float* pscore,
+                       int* pidx, int chunk_tiles, int stride, unsigned* rowthr) {
+  hipLaunchKernelGGL(partial128_kernel(mode), grid, dim3(THREADS), 0, a.stream,
+                     a.q, a.c, pscore, pidx, a.B, a.N, a.D, chunk_tiles, stride,
+                     rowthr, (unsigned long long*)nullptr);
+}
+
+using Partial8pFn = decltype(&cosine_topk_partial8p_t<9>);
+Partial8pFn partial8p_kernel(int mode) {
+  switch (mode) {
+    case 1: return cosine_topk_partial8p_t<1>;
+    case 6: return cosine_topk_partial8p_t<6>;
+    case 9: return cosine_topk_partial8p_t<9>;
+    case 12: return cosine_topk_partial8p_t<12>;
+    case 15: return cosine_topk_partial8p_t<15>;
   }
-  if (k == 1 && !use8p) {
-    // assignment fast path: per-row argmax epilogue (no lists/extraction)
-    hipLaunchKernelGGL((cosine_topk_partial_t<4>), grid, dim3(THREADS), 0, stream.stream(),
-                       (const bf16_t*)queries.data_ptr(), (const bf16_t*)corpus.data_ptr(),
-                       pscore.data_ptr<float>(), pidx.data_ptr<int>(),
-                       B, N, D, chunk_tiles, nchunks,
-                       (unsigned*)nullptr, (unsigned long long*)nullptr);
-  } else if (use8pe) {
-    // emission epilogue: candidates go to a per-row global buffer sized
-    // for ~8N/sample expected emissions with ~25x headroom
-    static const char* cenv = std::getenv("KAKVEDA_KNN_EMIT_CAP");
-    const long CAP = cenv ? std::atol(cenv) : 32768;
-    auto cand = torch::empty(
-        {(long)B, CAP},
-        torch::TensorOptions().dtype(torch::kInt64).device(queries.device()));
-    auto ccount = torch::zeros({B}, opts_i);
-    // per-(block, wave) global emission stash (see kernels_impl.h EPI 9)
-    auto estash = torch::empty(
-        {(long)nchunks * row_tiles * 8 * ESTASH_STRIDE},
-        torch::TensorOptions().dtype(torch::kUInt8).device(queries.device()));
-    // exact sample floor: merge the compact prepass partials into the
-    // true top-8 of the whole sampled column set, publish its 8th as the
-    // emission threshold (see publish_emission_floor). Block-per-row
-    // merge: the thread-per-row variant serial-scanned 2k entries per
-    // thread (0.9 ms/step at preg=256).
-    auto samp_s = torch::empty({(long)B, (long)KMAX}, opts_f);
-    auto samp_i = torch::empty(
-        {(long)B, (long)KMAX},
-        torch::TensorOptions().dtype(torch::kInt64).device(queries.device()));
-    if (prepass) {
-      hipLaunchKernelGGL(topk_merge, dim3(B), dim3(THREADS), 0,
-                         stream.stream(), ppre_s.data_ptr<float>(),
-                         ppre_i.data_ptr<int>(), samp_s.data_ptr<float>(),
-                         (long*)samp_i.data_ptr<int64_t>(), preg, KMAX);
-      hipLaunchKernelGGL(publish_emission_floor, dim3((B + 255) / 256),
-                         dim3(256), 0, stream.stream(),
-                         samp_s.data_ptr<float>(),
-                         (unsigned*)rowthr.data_ptr<int>(), B, KMAX - 1);
-    }
-    if (use_smallb) {
+  TORCH_CHECK(false, "no 256x256 kernel for EPI_MODE ", mode);
+}
+
+// cand/ccount/cap/estash are the emission epilogue's (modes 9/15) and
+// null/0 otherwise.
+void launch_partial8p(int mode, dim3 grid, const KnnArgs& a, float* pscore,
+                      int* pidx, int chunk_tiles, int nchunks, unsigned* rowthr,
+                      unsigned long long* cand, unsigned* ccount, long cap,
+                      char* estash) {
+  hipLaunchKernelGGL(partial8p_kernel(mode), grid, dim3(THREADS8), 0, a.stream,
+                     a.q, a.c, pscore, pidx, a.B, a.N, a.D, chunk_tiles, nchunks,
+                     rowthr, (unsigned long long*)nullptr, (float*)nullptr, cand,
+                     ccount, cap, estash);
+}
+
+torch::Tensor new_rowthr(const KnnArgs& a) {
+  auto rowthr = torch::empty({a.B}, a.i32());
+  hipLaunchKernelGGL(init_rowthr, dim3((a.B + 255) / 256), dim3(256), 0,
+                     a.stream, (unsigned*)rowthr.data_ptr<int>(), a.B);
+  return rowthr;
+}
+
+// Emission floors: a prepass over the first PRE_TILES*preg column tiles
+// writes a COMPACT [B][preg][KMAX] partial buffer of its own (so the floor
+// merge scans only what the prepass produced); topk_merge folds it into the
+// exact top-8 of the whole sampled column set, whose 8th is published as
+// the per-row emission threshold (see publish_emission_floor).
+struct Floors {
+  torch::Tensor rowthr, samp_s, samp_i;
+};
+
+Floors run_emission_floors(const KnnArgs& a, int preg, int prepass_mode) {
+  Floors f{new_rowthr(a), torch::empty({(long)a.B, (long)KMAX}, a.f32()),
+           torch::empty({(long)a.B, (long)KMAX}, a.i64())};
+  auto ppre_s = torch::empty({(long)a.B * preg * KMAX}, a.f32());
+  auto ppre_i = torch::empty({(long)a.B * preg * KMAX}, a.i32());
+  // the prepass always runs the 128-row-tile kernel, also under the
+  // 256-row-tile 8p main launch
+  launch_partial128(prepass_mode, dim3(preg, (a.B + BM - 1) / BM), a,
+                    ppre_s.data_ptr<float>(), ppre_i.data_ptr<int>(), PRE_TILES,
+                    preg, (unsigned*)f.rowthr.data_ptr<int>());
+  // block-per-row merge: the thread-per-row variant serial-scanned 2k
+  // entries per thread (0.9 ms/step at preg=256)
+  hipLaunchKernelGGL(topk_merge, dim3(a.B), dim3(THREADS), 0, a.stream,
+                     ppre_s.data_ptr<float>(), ppre_i.data_ptr<int>(),
+                     f.samp_s.data_ptr<float>(),
+                     (long*)f.samp_i.data_ptr<int64_t>(), preg, KMAX);
+  hipLaunchKernelGGL(publish_emission_floor, dim3((a.B + 255) / 256), dim3(256),
+                     0, a.stream, f.samp_s.data_ptr<float>(),
+                     (unsigned*)f.rowthr.data_ptr<int>(), a.B, KMAX - 1);
+  return f;
+}
+
+// Emission outputs: per-row candidate buffer + counts, and the per-(block,
+// wave) global stash of the 8p cold path (see kernels_impl.h EPI_MODE 9).
+struct EmitBufs {
+  torch::Tensor cand, ccount, estash;
+};
+
+EmitBufs new_emit_bufs(const KnnArgs& a, long cap, const Chunking& ch) {
+  return {torch::empty({(long)a.B, cap}, a.i64()), torch::zeros({a.B}, a.i32()),
+          torch::empty({(long)ch.nchunks * ch.row_tiles * 8 * ESTASH_STRIDE},
+                       torch::TensorOptions().dtype(torch::kUInt8).device(a.dev))};
+}
+
+void launch_emit8p(int mode, const KnnArgs& a, const Chunking& ch,
+                   torch::Tensor& pscore, torch::Tensor& pidx,
+                   const torch::Tensor& rowthr, EmitBufs& e, long cap) {
+  launch_partial8p(mode, dim3(ch.nchunks, ch.row_tiles), a,
+                   pscore.data_ptr<float>(), pidx.data_ptr<int>(),
+                   ch.chunk_tiles, ch.nchunks, (unsigned*)rowthr.data_ptr<int>(),
+                   (unsigned long long*)e.cand.data_ptr<int64_t>(),
+                   (unsigned*)e.ccount.data_ptr<int>(), cap,
+                   (char*)e.estash.data_ptr<uint8_t>());
+}
+
+std::tuple<torch::Tensor, torch::Tensor> cosine_topk_impl(
+    const torch::Tensor& queries, const torch::Tensor& corpus, int k, int N,
+    const KnnEnv& env, bool allow_emission) {
+  const KnnArgs a = knn_args(queries, corpus, N);
+  const int B = a.B;
+  const KnnPlan p = plan_cosine_topk(B, N, k, env, allow_emission);
+  const Chunking& ch = p.ch;
+
+  auto pscore = torch::empty({(long)B * ch.nchunks * KMAX}, a.f32());
+  auto pidx = torch::empty({(long)B * ch.nchunks * KMAX}, a.i32());
+  auto out_score = torch::empty({B, k}, a.f32());
+  auto out_idx = torch::empty({B, k}, a.i64());
+  const dim3 grid(ch.nchunks, ch.row_tiles);
+
+  if (p.merge == MergeKernel::Emit) {
+    // candidates go to a per-row global buffer sized for ~8N/sample
+    // expected emissions with ~25x headroom
+    const Floors f = p.prepass ? run_emission_floors(a, p.preg, p.prepass_mode)
+                               : Floors{new_rowthr(a), {}, {}};
+    EmitBufs e = new_emit_bufs(a, p.cap, ch);
+    if (p.main == MainKernel::SmallB) {
       // Default: the v4 8-lanes-per-row remap (same-box A/B at 10M:
       // +1.5% at B=1, +13.6% at B=4, exact parity — see
       // profiles/knn_kernel_history.md). KAKVEDA_SMALLB=2 reverts to the
-      // per-lane-row streaming kernel (v2/v3).
-      static const char* sbenv = std::getenv("KAKVEDA_SMALLB");
-      const long nblk = std::min((long)((N + 255) / 256), 8192L);
-      if (!(sbenv && sbenv[0] == '2'))
-        hipLaunchKernelGGL(smallb_emit_kernel_v4, dim3((int)nblk), dim3(256),
-                           (size_t)B * D * 2, stream.stream(),
-                           (const bf16_t*)queries.data_ptr(),
-                           (const bf16_t*)corpus.data_ptr(), B, (long)N, D,
-                           (const unsigned*)rowthr.data_ptr<int>(),
-                           (unsigned long long*)cand.data_ptr<int64_t>(),
-                           (unsigned*)ccount.data_ptr<int>(), CAP);
-      else
-        hipLaunchKernelGGL(smallb_emit_kernel, dim3((int)nblk), dim3(256),
-                           (size_t)B * D * 2, stream.stream(),
-                           (const bf16_t*)queries.data_ptr(),
-                           (const bf16_t*)corpus.data_ptr(), B, (long)N, D,
-                           (const unsigned*)rowthr.data_ptr<int>(),
-                           (unsigned long long*)cand.data_ptr<int64_t>(),
-                           (unsigned*)ccount.data_ptr<int>(), CAP);
-    } else if (use8pv3)
-      hipLaunchKernelGGL((cosine_topk_partial8p_t<14>), grid, dim3(THREADS8),
-                         0, stream.stream(), (const bf16_t*)queries.data_ptr(),
-                         (const bf16_t*)corpus.data_ptr(),
-                         pscore.data_ptr<float>(), pidx.data_ptr<int>(),
-                         B, N, D, chunk_tiles, nchunks,
-                         (unsigned*)rowthr.data_ptr<int>(),
-                         (unsigned long long*)nullptr, (float*)nullptr,
-                         (unsigned long long*)cand.data_ptr<int64_t>(),
-                         (unsigned*)ccount.data_ptr<int>(), CAP,
-                         (char*)estash.data_ptr<uint8_t>());
-    else if (use8pv2)
-      hipLaunchKernelGGL((cosine_topk_partial8p_t<15>), grid, dim3(THREADS8),
-                         0, stream.stream(), (const bf16_t*)queries.data_ptr(),
-                         (const bf16_t*)corpus.data_ptr(),
-                         pscore.data_ptr<float>(), pidx.data_ptr<int>(),
-                         B, N, D, chunk_tiles, nchunks,
-                         (unsigned*)rowthr.data_ptr<int>(),
-                         (unsigned long long*)nullptr, (float*)nullptr,
-                         (unsigned long long*)cand.data_ptr<int64_t>(),
-                         (unsigned*)ccount.data_ptr<int>(), CAP,
-                         (char*)estash.data_ptr<uint8_t>());
-    else
-      hipLaunchKernelGGL((cosine_topk_partial8p_t<9>), grid, dim3(THREADS8), 0,
-                         stream.stream(), (const bf16_t*)queries.data_ptr(),
-                         (const bf16_t*)corpus.data_ptr(),
-                         pscore.data_ptr<float>(), pidx.data_ptr<int>(),
-                         B, N, D, chunk_tiles, nchunks,
-                         (unsigned*)rowthr.data_ptr<int>(),
-                         (unsigned long long*)nullptr, (float*)nullptr,
-                         (unsigned long long*)cand.data_ptr<int64_t>(),
-                         (unsigned*)ccount.data_ptr<int>(), CAP,
-                         (char*)estash.data_ptr<uint8_t>());
-    hipLaunchKernelGGL(emit_merge_topk, dim3(B), dim3(256), 0, stream.stream(),
-                       (const unsigned long long*)cand.data_ptr<int64_t>(),
-                       (const unsigned*)ccount.data_ptr<int>(),
+      // per-lane-row streaming kernel (v2).
+      hipLaunchKernelGGL(p.mode == 2 ? smallb_emit_kernel : smallb_emit_kernel_v4,
+                         dim3(p.smallb_blocks), dim3(256), (size_t)B * a.D * 2,
+                         a.stream, a.q, a.c, B, (long)N, a.D,
+                         (const unsigned*)f.rowthr.data_ptr<int>(),
+                         (unsigned long long*)e.cand.data_ptr<int64_t>(),
+                         (unsigned*)e.ccount.data_ptr<int>(), p.cap);
+    } else {
+      launch_emit8p(p.mode, a, ch, pscore, pidx, f.rowthr, e, p.cap);
+    }
+    hipLaunchKernelGGL(emit_merge_topk, dim3(B), dim3(256), 0, a.stream,
+                       (const unsigned long long*)e.cand.data_ptr<int64_t>(),
+                       (const unsigned*)e.ccount.data_ptr<int>(),
                        out_score.data_ptr<float>(),
-                       (long*)out_idx.data_ptr<int64_t>(), B, CAP, (int)k);
+                       (long*)out_idx.data_ptr<int64_t>(), B, p.cap, k);
     // exactness guard (statistically never taken with prepass floors):
     // an overflowed row means emission skipped stores — rerun the whole
     // batch through the list-epilogue production kernel
-    const long mx = (long)ccount.max().item<int>();
-    static const char* denv = std::getenv("KAKVEDA_KNN_EMIT_DEBUG");
-    if (denv && denv[0] == '1')
+    const long mx = (long)e.ccount.max().item<int>();
+    if (env.emit_debug)
       printf("emit: rows=%d max=%ld mean=%.1f cap=%ld%s\n", B, mx,
-             ccount.to(torch::kFloat32).mean().item<float>(), CAP,
-             mx > CAP ? "  FALLBACK" : "");
-    if (mx > CAP) {
+             e.ccount.to(torch::kFloat32).mean().item<float>(), p.cap,
+             mx > p.cap ? "  FALLBACK" : "");
+    if (mx > p.cap) {
       static bool warned = false;
       if (!warned) {
         warned = true;
         fprintf(stderr,
                 "[kakveda] emission candidate overflow (max=%ld > cap=%ld) — "
                 "falling back to the list-epilogue kernel for this batch\n",
-                mx, CAP);
+                mx, p.cap);
       }
-      emit_fallback = 1;
-      auto r = cosine_topk(queries, corpus, k, valid_n);
-      emit_fallback = 0;
-      return r;
+      return cosine_topk_impl(queries, corpus, k, N, env, false);
     }
     return {out_score, out_idx};
-  } else if (use8pq) {
-    hipLaunchKernelGGL((cosine_topk_partial8p_t<7>), grid, dim3(THREADS8), 0, stream.stream(),
-                       (const bf16_t*)queries.data_ptr(), (const bf16_t*)corpus.data_ptr(),
-                       pscore.data_ptr<float>(), pidx.data_ptr<int>(),
-                       B, N, D, chunk_tiles, nchunks,
-                       (unsigned*)rowthr.data_ptr<int>(), (unsigned long long*)nullptr);
-    // (slab: probe-only EPI_MODE 5 path)
-  } else if (use8pbl) {
-    hipLaunchKernelGGL((cosine_topk_partial8p_t<6>), grid, dim3(THREADS8), 0, stream.stream(),
-                       (const bf16_t*)queries.data_ptr(), (const bf16_t*)corpus.data_ptr(),
-                       pscore.data_ptr<float>(), pidx.data_ptr<int>(),
-                       B, N, D, chunk_tiles, nchunks,
-                       (unsigned*)rowthr.data_ptr<int>(), (unsigned long long*)nullptr);
-    // (slab: probe-only EPI_MODE 5 path)
-  } else if (use8p) {
-    hipLaunchKernelGGL((cosine_topk_partial8p_t<0>), grid, dim3(THREADS8), 0, stream.stream(),
-                       (const bf16_t*)queries.data_ptr(), (const bf16_t*)corpus.data_ptr(),
-                       pscore.data_ptr<float>(), pidx.data_ptr<int>(),
-                       B, N, D, chunk_tiles, nchunks,
-                       (unsigned*)rowthr.data_ptr<int>(), (unsigned long long*)nullptr);
-    // (slab: probe-only EPI_MODE 5 path)
-  } else if (epi == 7) {
-    hipLaunchKernelGGL((cosine_topk_partial_t<7>), grid, dim3(THREADS), 0, stream.stream(),
-                       (const bf16_t*)queries.data_ptr(), (const bf16_t*)corpus.data_ptr(),
-                       pscore.data_ptr<float>(), pidx.data_ptr<int>(),
-                       B, N, D, chunk_tiles, nchunks,
-                       (unsigned*)rowthr.data_ptr<int>(), (unsigned long long*)nullptr);
-  } else if (epi == 8) {
-    hipLaunchKernelGGL((cosine_topk_partial_t<8>), grid, dim3(THREADS), 0, stream.stream(),
-                       (const bf16_t*)queries.data_ptr(), (const bf16_t*)corpus.data_ptr(),
-                       pscore.data_ptr<float>(), pidx.data_ptr<int>(),
-                       B, N, D, chunk_tiles, nchunks,
-                       (unsigned*)rowthr.data_ptr<int>(), (unsigned long long*)nullptr);
-  } else if (epi == 9) {
-    hipLaunchKernelGGL((cosine_topk_partial_t<9>), grid, dim3(THREADS), 0, stream.stream(),
-                       (const bf16_t*)queries.data_ptr(), (const bf16_t*)corpus.data_ptr(),
-                       pscore.data_ptr<float>(), pidx.data_ptr<int>(),
-                       B, N, D, chunk_tiles, nchunks,
-                       (unsigned*)rowthr.data_ptr<int>(), (unsigned long long*)nullptr);
-  } else if (epi == 11) {
-    hipLaunchKernelGGL((cosine_topk_partial_t<11>), grid, dim3(THREADS), 0, stream.stream(),
-                       (const bf16_t*)queries.data_ptr(), (const bf16_t*)corpus.data_ptr(),
-                       pscore.data_ptr<float>(), pidx.data_ptr<int>(),
-                       B, N, D, chunk_tiles, nchunks,
-                       (unsigned*)rowthr.data_ptr<int>(), (unsigned long long*)nullptr);
-  } else {
-    hipLaunchKernelGGL(cosine_topk_partial, grid, dim3(THREADS), 0, stream.stream(),
-                       (const bf16_t*)queries.data_ptr(), (const bf16_t*)corpus.data_ptr(),
-                       pscore.data_ptr<float>(), pidx.data_ptr<int>(),
-                       B, N, D, chunk_tiles, nchunks,
-                       (unsigned*)rowthr.data_ptr<int>(), (unsigned long long*)nullptr);
   }
-  if (nchunks * KMAX <= 1024) {
-    // few candidates per row: one thread per row beats the block-per-row
-    // merge (whose thread-0 serial scan dominates at large B)
+
+  auto rowthr = new_rowthr(a);
+  unsigned* const thr = (unsigned*)rowthr.data_ptr<int>();
+  // Threshold pre-pass: one cheap launch over the first PRE_TILES*preg
+  // column tiles fills each row's lists from a ~4k-column sample and
+  // publishes their minima into rowthr, so the main launch's blocks all
+  // start with near-converged pruning thresholds instead of each paying
+  // the bootstrap insert storm (measured: warm thresholds are worth
+  // ~10% end-to-end; the sample scan is ~0.5% extra work, its partial
+  // writes land in slots the main launch overwrites).
+  if (p.prepass)
+    launch_partial128(p.prepass_mode, dim3(p.preg, (B + BM - 1) / BM), a,
+                      pscore.data_ptr<float>(), pidx.data_ptr<int>(), PRE_TILES,
+                      ch.nchunks, thr);
+  if (p.main == MainKernel::Stash8p)
+    launch_partial8p(p.mode, grid, a, pscore.data_ptr<float>(),
+                     pidx.data_ptr<int>(), ch.chunk_tiles, ch.nchunks, thr,
+                     nullptr, nullptr, 0, nullptr);
+  else  // List128, or Argmax128 (k=1: per-row max, no thresholds)
+    launch_partial128(p.mode, grid, a, pscore.data_ptr<float>(),
+                      pidx.data_ptr<int>(), ch.chunk_tiles, ch.nchunks,
+                      p.main == MainKernel::Argmax128 ? nullptr : thr);
+  if (p.merge == MergeKernel::Small)
     hipLaunchKernelGGL(topk_merge_small, dim3((B + 255) / 256), dim3(256), 0,
-                       stream.stream(), pscore.data_ptr<float>(),
-                       pidx.data_ptr<int>(), out_score.data_ptr<float>(),
-                       (long*)out_idx.data_ptr<int64_t>(), B, nchunks, (int)k);
-  } else {
-    hipLaunchKernelGGL(topk_merge, dim3(B), dim3(THREADS), 0, stream.stream(),
+                       a.stream, pscore.data_ptr<float>(), pidx.data_ptr<int>(),
+                       out_score.data_ptr<float>(),
+                       (long*)out_idx.data_ptr<int64_t>(), B, ch.nchunks, k);
+  else
+    hipLaunchKernelGGL(topk_merge, dim3(B), dim3(THREADS), 0, a.stream,
                        pscore.data_ptr<float>(), pidx.data_ptr<int>(),
-                       out_score.data_ptr<float>(), (long*)out_idx.data_ptr<int64_t>(),
-                       nchunks, (int)k);
-  }
+                       out_score.data_ptr<float>(),
+                       (long*)out_idx.data_ptr<int64_t>(), ch.nchunks, k);
   return {out_score, out_idx};
+}
+
+}  // namespace
+
+std::tuple<torch::Tensor, torch::Tensor> cosine_topk(
+    torch::Tensor queries, torch::Tensor corpus, int64_t k, int64_t valid_n) {
+  check_bf16_2d(queries, "queries");
+  check_bf16_2d(corpus, "corpus");
+  const int D = queries.size(1);
+  const int N = (int)valid_n;
+  TORCH_CHECK(corpus.size(1) == D, "dim mismatch");
+  TORCH_CHECK(N >= 1 && N <= corpus.size(0), "valid_n out of range");
+  TORCH_CHECK(D % BK == 0, "D must be a multiple of ", BK);
+  TORCH_CHECK(k >= 1 && k <= KMAX, "k must be in [1,", KMAX, "]");
+  // parse -> plan -> allocate -> launch. The KAKVEDA_KNN_* environment is
+  // read once per process; an unrecognised selection throws here, before
+  // anything is launched (knn_plan.h).
+  static const KnnEnv env = parse_knn_env(std::getenv);
+  return cosine_topk_impl(queries, corpus, (int)k, N, env, true);
 }
 
 void l2normalize_(torch::Tensor t, int64_t start_row, int64_t end_row) {
@@ -488,38 +371,9 @@ std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> floor_probe(
   // rowthr u32 [B]) for offline comparison against a torch reference.
   check_bf16_2d(queries, "queries");
   check_bf16_2d(corpus, "corpus");
-  const int B = queries.size(0);
-  const int D = queries.size(1);
-  const int N = corpus.size(0);
-  const int preg = ((int)pregq) & ~7;
-  auto opts_f = torch::TensorOptions().dtype(torch::kFloat32).device(queries.device());
-  auto opts_i = torch::TensorOptions().dtype(torch::kInt32).device(queries.device());
-  auto rowthr = torch::empty({B}, opts_i);
-  auto ppre_s = torch::empty({(long)B * preg * KMAX}, opts_f);
-  auto ppre_i = torch::empty({(long)B * preg * KMAX}, opts_i);
-  auto samp_s = torch::empty({(long)B, (long)KMAX}, opts_f);
-  auto samp_i = torch::empty(
-      {(long)B, (long)KMAX},
-      torch::TensorOptions().dtype(torch::kInt64).device(queries.device()));
-  auto stream = c10::hip::getCurrentHIPStream();
-  hipLaunchKernelGGL(init_rowthr, dim3((B + 255) / 256), dim3(256), 0,
-                     stream.stream(), (unsigned*)rowthr.data_ptr<int>(), B);
-  constexpr int PRE_TILES = 8;
-  dim3 pgrid(preg, (B + BM - 1) / BM);
-  hipLaunchKernelGGL((cosine_topk_partial_t<11>), pgrid, dim3(THREADS), 0,
-                     stream.stream(), (const bf16_t*)queries.data_ptr(),
-                     (const bf16_t*)corpus.data_ptr(), ppre_s.data_ptr<float>(),
-                     ppre_i.data_ptr<int>(), B, N, D, PRE_TILES, preg,
-                     (unsigned*)rowthr.data_ptr<int>(),
-                     (unsigned long long*)nullptr);
-  hipLaunchKernelGGL(topk_merge, dim3(B), dim3(THREADS), 0, stream.stream(),
-                     ppre_s.data_ptr<float>(), ppre_i.data_ptr<int>(),
-                     samp_s.data_ptr<float>(),
-                     (long*)samp_i.data_ptr<int64_t>(), preg, KMAX);
-  hipLaunchKernelGGL(publish_emission_floor, dim3((B + 255) / 256), dim3(256),
-                     0, stream.stream(), samp_s.data_ptr<float>(),
-                     (unsigned*)rowthr.data_ptr<int>(), B, KMAX - 1);
-  return {samp_s, samp_i, rowthr};
+  const KnnArgs a = knn_args(queries, corpus, (int)corpus.size(0));
+  const Floors f = run_emission_floors(a, ((int)pregq) & ~7, 11);
+  return {f.samp_s, f.samp_i, f.rowthr};
 }
 
 std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> emit_counts_probe(
@@ -529,123 +383,44 @@ std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> emit_counts_probe(
   // inspection of which rows overcount.
   check_bf16_2d(queries, "queries");
   check_bf16_2d(corpus, "corpus");
-  const int B = queries.size(0);
-  const int D = queries.size(1);
-  const int N = corpus.size(0);
-  const int preg = ((int)pregq) & ~7;
-  auto opts_f = torch::TensorOptions().dtype(torch::kFloat32).device(queries.device());
-  auto opts_i = torch::TensorOptions().dtype(torch::kInt32).device(queries.device());
-  auto rowthr = torch::empty({B}, opts_i);
-  auto ppre_s = torch::empty({(long)B * preg * KMAX}, opts_f);
-  auto ppre_i = torch::empty({(long)B * preg * KMAX}, opts_i);
-  auto samp_s = torch::empty({(long)B, (long)KMAX}, opts_f);
-  auto samp_i = torch::empty(
-      {(long)B, (long)KMAX},
-      torch::TensorOptions().dtype(torch::kInt64).device(queries.device()));
-  auto stream = c10::hip::getCurrentHIPStream();
-  hipLaunchKernelGGL(init_rowthr, dim3((B + 255) / 256), dim3(256), 0,
-                     stream.stream(), (unsigned*)rowthr.data_ptr<int>(), B);
-  constexpr int PRE_TILES = 8;
-  dim3 pgrid(preg, (B + BM - 1) / BM);
-  hipLaunchKernelGGL((cosine_topk_partial_t<11>), pgrid, dim3(THREADS), 0,
-                     stream.stream(), (const bf16_t*)queries.data_ptr(),
-                     (const bf16_t*)corpus.data_ptr(), ppre_s.data_ptr<float>(),
-                     ppre_i.data_ptr<int>(), B, N, D, PRE_TILES, preg,
-                     (unsigned*)rowthr.data_ptr<int>(),
-                     (unsigned long long*)nullptr);
-  hipLaunchKernelGGL(topk_merge, dim3(B), dim3(THREADS), 0, stream.stream(),
-                     ppre_s.data_ptr<float>(), ppre_i.data_ptr<int>(),
-                     samp_s.data_ptr<float>(),
-                     (long*)samp_i.data_ptr<int64_t>(), preg, KMAX);
-  hipLaunchKernelGGL(publish_emission_floor, dim3((B + 255) / 256), dim3(256),
-                     0, stream.stream(), samp_s.data_ptr<float>(),
-                     (unsigned*)rowthr.data_ptr<int>(), B, KMAX - 1);
-  const int row_tiles = (B + BM8 - 1) / BM8;
-  const int ntiles = (N + BN8 - 1) / BN8;
-  long want = ((long)ntiles * row_tiles + 511) / 512;
-  const int chunk_tiles = (int)std::max(4L, std::min(want, 128L));
-  const int nchunks = ((ntiles + chunk_tiles - 1) / chunk_tiles + 7) & ~7;
+  const KnnArgs a = knn_args(queries, corpus, (int)corpus.size(0));
+  const Floors f = run_emission_floors(a, ((int)pregq) & ~7, 11);
+  const Chunking ch = chunking(a.B, a.N, BM8, default_target(BM8));
   const long CAP = 32768;
-  auto pscore = torch::empty({(long)B * nchunks * KMAX}, opts_f);
-  auto pidx = torch::empty({(long)B * nchunks * KMAX}, opts_i);
-  auto cand = torch::empty(
-      {(long)B, CAP},
-      torch::TensorOptions().dtype(torch::kInt64).device(queries.device()));
-  auto ccount = torch::zeros({B}, opts_i);
-  auto estash = torch::empty(
-      {(long)nchunks * row_tiles * 8 * ESTASH_STRIDE},
-      torch::TensorOptions().dtype(torch::kUInt8).device(queries.device()));
-  dim3 grid(nchunks, row_tiles);
-  hipLaunchKernelGGL((cosine_topk_partial8p_t<9>), grid, dim3(THREADS8), 0,
-                     stream.stream(), (const bf16_t*)queries.data_ptr(),
-                     (const bf16_t*)corpus.data_ptr(), pscore.data_ptr<float>(),
-                     pidx.data_ptr<int>(), B, N, D, chunk_tiles, nchunks,
-                     (unsigned*)rowthr.data_ptr<int>(),
-                     (unsigned long long*)nullptr, (float*)nullptr,
-                     (unsigned long long*)cand.data_ptr<int64_t>(),
-                     (unsigned*)ccount.data_ptr<int>(), CAP,
-                     (char*)estash.data_ptr<uint8_t>());
-  return {ccount, cand, rowthr};
+  auto pscore = torch::empty({(long)a.B * ch.nchunks * KMAX}, a.f32());
+  auto pidx = torch::empty({(long)a.B * ch.nchunks * KMAX}, a.i32());
+  EmitBufs e = new_emit_bufs(a, CAP, ch);
+  launch_emit8p(9, a, ch, pscore, pidx, f.rowthr, e, CAP);
+  return {e.ccount, e.cand, f.rowthr};
 }
 
 double probe8p(torch::Tensor queries, torch::Tensor corpus, int64_t mode,
                int64_t iters) {
   // Timing probe for 8p epilogue isolation (profiles/knn_kernel_history):
   // mode 1 = no epilogue (GEMM core), 12 = hot sweep only (worst case:
-  // null thresholds make every ballot fire), 9 = full emission with
-  // -inf floors (bootstrap worst case). Returns ms per launch.
+  // null thresholds make every ballot fire). Neither touches the emission
+  // buffers, so none are passed. Returns ms per launch.
   check_bf16_2d(queries, "queries");
   check_bf16_2d(corpus, "corpus");
-  const int B = queries.size(0);
-  const int D = queries.size(1);
-  const int N = corpus.size(0);
-  const int row_tiles = (B + BM8 - 1) / BM8;
-  const int ntiles = (N + BN8 - 1) / BN8;
-  long want = ((long)ntiles * row_tiles + 511) / 512;
-  const int chunk_tiles = (int)std::max(4L, std::min(want, 128L));
-  const int nchunks = ((ntiles + chunk_tiles - 1) / chunk_tiles + 7) & ~7;
-  auto opts_f = torch::TensorOptions().dtype(torch::kFloat32).device(queries.device());
-  auto opts_i = torch::TensorOptions().dtype(torch::kInt32).device(queries.device());
-  auto pscore = torch::empty({(long)B * nchunks * KMAX}, opts_f);
-  auto pidx = torch::empty({(long)B * nchunks * KMAX}, opts_i);
-  auto cand = torch::empty({(long)B, 65536},
-                           torch::TensorOptions().dtype(torch::kInt64).device(queries.device()));
-  auto ccount = torch::zeros({B}, opts_i);
-  auto stream = c10::hip::getCurrentHIPStream();
-  dim3 grid(nchunks, row_tiles);
-  auto launch = [&](int md) {
-    if (md == 1)
-      hipLaunchKernelGGL((cosine_topk_partial8p_t<1>), grid, dim3(THREADS8), 0,
-                         stream.stream(), (const bf16_t*)queries.data_ptr(),
-                         (const bf16_t*)corpus.data_ptr(), pscore.data_ptr<float>(),
-                         pidx.data_ptr<int>(), B, N, D, chunk_tiles, nchunks,
-                         (unsigned*)nullptr, (unsigned long long*)nullptr,
-                         (float*)nullptr, (unsigned long long*)cand.data_ptr<int64_t>(),
-                         (unsigned*)ccount.data_ptr<int>(), 65536);
-    else if (md == 12)
-      hipLaunchKernelGGL((cosine_topk_partial8p_t<12>), grid, dim3(THREADS8), 0,
-                         stream.stream(), (const bf16_t*)queries.data_ptr(),
-                         (const bf16_t*)corpus.data_ptr(), pscore.data_ptr<float>(),
-                         pidx.data_ptr<int>(), B, N, D, chunk_tiles, nchunks,
-                         (unsigned*)nullptr, (unsigned long long*)nullptr,
-                         (float*)nullptr, (unsigned long long*)cand.data_ptr<int64_t>(),
-                         (unsigned*)ccount.data_ptr<int>(), 65536);
-    else
-      hipLaunchKernelGGL((cosine_topk_partial8p_t<9>), grid, dim3(THREADS8), 0,
-                         stream.stream(), (const bf16_t*)queries.data_ptr(),
-                         (const bf16_t*)corpus.data_ptr(), pscore.data_ptr<float>(),
-                         pidx.data_ptr<int>(), B, N, D, chunk_tiles, nchunks,
-                         (unsigned*)nullptr, (unsigned long long*)nullptr,
-                         (float*)nullptr, (unsigned long long*)cand.data_ptr<int64_t>(),
-                         (unsigned*)ccount.data_ptr<int>(), 65536);
+  TORCH_CHECK(mode == 1 || mode == 12,
+              "probe8p mode must be 1 (GEMM core) or 12 (hot sweep), got ", mode);
+  const KnnArgs a = knn_args(queries, corpus, (int)corpus.size(0));
+  const Chunking ch = chunking(a.B, a.N, BM8, default_target(BM8));
+  auto pscore = torch::empty({(long)a.B * ch.nchunks * KMAX}, a.f32());
+  auto pidx = torch::empty({(long)a.B * ch.nchunks * KMAX}, a.i32());
+  auto launch = [&] {
+    launch_partial8p((int)mode, dim3(ch.nchunks, ch.row_tiles), a,
+                     pscore.data_ptr<float>(), pidx.data_ptr<int>(),
+                     ch.chunk_tiles, ch.nchunks, nullptr, nullptr, nullptr, 0,
+                     nullptr);
   };
-  launch((int)mode);  // warmup
+  launch();  // warmup
   hipEvent_t e0, e1;
   hipEventCreate(&e0);
   hipEventCreate(&e1);
-  hipEventRecord(e0, stream.stream());
-  for (long i = 0; i < iters; ++i) launch((int)mode);
-  hipEventRecord(e1, stream.stream());
+  hipEventRecord(e0, a.stream);
+  for (long i = 0; i < iters; ++i) launch();
+  hipEventRecord(e1, a.stream);
   hipEventSynchronize(e1);
   float ms = 0.f;
   hipEventElapsedTime(&ms, e0, e1);

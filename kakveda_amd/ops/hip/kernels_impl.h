@@ -8,8 +8,9 @@
 // reference's per-request TF-IDF refit + full-corpus cosine
 // (reference: services/shared/similarity.py:14-20, services/gfkb/app.py:79-102).
 //
-// Design (MI355X-first, see /opt/skills/guides/cdna_hip_programming.md):
-// - cosine_topk_partial: one workgroup owns a (128-query row tile x corpus
+// Design (MI355X-first; "guide" tags such as T1, G13 or rule 21 name
+// techniques of the CDNA HIP programming guide this was written against):
+// - cosine_topk_partial_t: one workgroup owns a (128-query row tile x corpus
 //   chunk). Per 128-column tile it runs an MFMA GEMM (mfma_f32_16x16x32_bf16,
 //   4 waves x 64x64 output each, BK=64 K-steps, double-buffered LDS staged
 //   with global_load_lds_dwordx4) and feeds the scores into an LDS-resident
@@ -25,6 +26,7 @@
 
 #include <hip/hip_runtime.h>
 #include <cstdint>
+#include "knn_plan.h"  // BM/BN/BM8/BN8/KMAX: shared with the host dispatch plan
 
 #define DEVINL __device__ __forceinline__
 
@@ -34,11 +36,8 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 namespace kakveda {
 
-constexpr int BM = 128;        // query rows per block
-constexpr int BN = 128;        // corpus cols per tile
 constexpr int BK = 64;         // K depth per LDS stage
 constexpr int THREADS = 256;   // 4 waves
-constexpr int KMAX = 8;        // top-k list capacity per row
 constexpr int TILE_BYTES = BM * BK * 2;  // 16 KiB (BM==BN)
 constexpr float NEG_INF = -1e30f;
 
@@ -91,88 +90,11 @@ DEVINL bf16x8 read_frag(const char* lds_tile, int row, int slot) {
   return *(const bf16x8*)(lds_tile + row * 128 + s_phys * 16);
 }
 
-// Generalised variants: tiles of [128 rows][NKK*32 k] (row = NKK*64 bytes).
-template <int NKK>
-DEVINL void stage_tile_n(const bf16_t* __restrict__ src, int row0, int row_max,
-                         long row_bytes, int ktile_byte, char* lds_tile,
-                         int wid, int lane) {
-  constexpr int ROWB = NKK * 64;     // bytes per tile row
-  constexpr int SLOTS = NKK * 4;     // 16-B slots per row
-#pragma unroll
-  for (int i = 0; i < 2 * NKK; ++i) {
-    const int lds_off = wid * (2 * NKK) * 1024 + i * 1024;
-    const int P = lds_off + lane * 16;
-    const int r = P / ROWB;
-    const int s_phys = (P >> 4) % SLOTS;
-    const int s_log = NKK == 2 ? (s_phys ^ (r & 7)) : (s_phys ^ ((r >> 2) & 3));
-    const int gr = min(row0 + r, row_max);
-    const char* gaddr =
-        (const char*)src + (size_t)gr * row_bytes + ktile_byte + s_log * 16;
-    glds16(gaddr, lds_tile + lds_off);
-  }
-}
-
-template <int NKK>
-DEVINL bf16x8 read_frag_n(const char* lds_tile, int row, int slot) {
-  const int s_phys = NKK == 2 ? (slot ^ (row & 7)) : (slot ^ ((row >> 2) & 3));
-  return *(const bf16x8*)(lds_tile + row * (NKK * 64) + s_phys * 16);
-}
-
-
 // Extraction for one qualifying (row, col-half): deliberately __noinline__
 // so the 16 unrolled epilogue bodies don't get their candidate values
 // hoisted live simultaneously (measured: inlining costs 100+ VGPRs and
-// ~850 B/lane of scratch spill).
-// Ballot-leader variant: no per-insert wave argmax reduce — each loop
-// iteration picks the lowest qualifying lane, which inserts its own best
-// candidate. Fewer cross-lane ops per insert; insertion order is
-// arbitrary (list semantics identical).
-template <bool PUBLISH>
-__device__ __noinline__ void topk_extract_group_bl(
-    volatile float* vsc, volatile int* vix, int lbase, float rwarm,
-    float w0, float w1, float w2, float w3, int colb, int N_unused, int lane,
-    int g, unsigned* rowthr, int growp1) {
-  float rmin = fmaxf(vsc[lbase], rwarm);
-  while (true) {
-    float b = w0;
-    int bn = 0;
-    if (w1 > b) { b = w1; bn = 1; }
-    if (w2 > b) { b = w2; bn = 2; }
-    if (w3 > b) { b = w3; bn = 3; }
-    const unsigned long long ball =
-        __ballot(b > rmin) & (0xFFFFull << (g * 16));
-    if (!ball) break;
-    const int leader = __ffsll(ball) - 1;
-    if (lane == leader) {
-      float nmn = b;
-      int nmp = 0;
-#pragma unroll
-      for (int q = 1; q < KMAX; ++q) {
-        const float s = vsc[lbase + q];
-        if (s < nmn) { nmn = s; nmp = q; }
-      }
-      const int gcol = colb + bn * 16;
-      if (nmp == 0) {
-        vsc[lbase] = b;
-        vix[lbase] = gcol;
-      } else {
-        const int mi2 = vix[lbase + nmp];
-        vsc[lbase] = nmn;
-        vix[lbase] = mi2;
-        vsc[lbase + nmp] = b;
-        vix[lbase + nmp] = gcol;
-      }
-      if (bn == 0) w0 = NEG_INF;
-      else if (bn == 1) w1 = NEG_INF;
-      else if (bn == 2) w2 = NEG_INF;
-      else w3 = NEG_INF;
-      if (PUBLISH && rowthr != nullptr && nmn > NEG_INF && growp1 > 0)
-        atomicMax(&rowthr[growp1 - 1], enc_f32(nmn));
-    }
-    rmin = fmaxf(vsc[lbase], rwarm);  // same-wave LDS program order
-  }
-}
-
+// ~850 B/lane of scratch spill). Each loop iteration a wave argmax reduce
+// picks the group's best remaining candidate; its lane inserts it.
 template <bool PUBLISH>
 __device__ __noinline__ void topk_extract_group(
     volatile float* vsc, volatile int* vix, int lbase, float rwarm,
@@ -228,28 +150,32 @@ __device__ __noinline__ void topk_extract_group(
 //   grid.x = nchunks, grid.y = ceil(B/128), block = 256 threads.
 //   partial_score/partial_idx: [B][nchunks][KMAX]
 // ---------------------------------------------------------------------------
-// EPI_MODE: 0 full top-k (volatile-LDS thresholds, immediate extraction),
-// 1 GEMM-only ablation, 2 pre-check only (NOTE: its empty taken-branch
-// lets the compiler dead-code-eliminate the MFMAs — not a valid ceiling;
-// use 1), 3 full+stats, 4 argmax (k=1 fast path: per-row max, no
-// lists/extraction), 6 ballot-leader extraction, 7 deferred
-// register-threshold epilogue (extraction after the tile barrier;
-// measured slower), 8 register-cached thresholds + call-only extraction,
-// 9 = 8 + inline single-insert fast path, 10 = 9 + bootstrap bypass
-// (parity), 11 = 9 with a masked-__ballot pre-check instead of the
-// 4-deep shfl_xor max reduce — the PRODUCTION DEFAULT (754 TF vs 642
-// for mode 0 at B=4096 x N=2M; see profiles/knn_kernel_history.md).
-template <int EPI_MODE, int NKK = 2>  // NKK: 32-deep K steps per LDS stage (2 -> BK=64)
-__global__ __launch_bounds__(THREADS, 4 - NKK) void cosine_topk_partial_t(
+// EPI_MODE (numbering is historical; the pruned variants and their
+// verdicts are in profiles/knn_kernel_history.md):
+//   0  full top-k: volatile-LDS thresholds, call-only extraction
+//   1  GEMM-only ablation (tools/knn_probe.hip)
+//   4  argmax (k=1 fast path: per-row max, no lists/extraction)
+//   8  register-cached thresholds + call-only extraction
+//   9  = 8 + inline single-insert fast path
+//   11 = 9 with a masked-__ballot pre-check instead of the 4-deep
+//      shfl_xor max reduce — the PRODUCTION DEFAULT (754 TF vs 642 for
+//      mode 0 at B=4096 x N=2M)
+// `stats` is unused (it belonged to a pruned counting mode) and stays in
+// the signature so kernel symbols and kernarg offsets do not move.
+template <int EPI_MODE>
+__global__ __launch_bounds__(THREADS, 2) void cosine_topk_partial_t(
     const bf16_t* __restrict__ Q, const bf16_t* __restrict__ C,
     float* __restrict__ partial_score, int* __restrict__ partial_idx,
     int B, int N, int D, int chunk_tiles, int nchunks,
     unsigned* rowthr = nullptr, unsigned long long* stats = nullptr) {
+  constexpr bool REG_THR = EPI_MODE == 8 || EPI_MODE == 9 || EPI_MODE == 11;
+  constexpr bool INLINE_INSERT = EPI_MODE == 9 || EPI_MODE == 11;
+  constexpr bool BALLOT_CHECK = EPI_MODE == 11;
   // LDS: 4 x 16 KiB staging (A,B double-buffered) + per-(row, col-half)
   // private top-k lists. 80 KiB total -> 2 blocks/CU. The lists are
   // private to the one wave that computes that (row-half, col-half), so
   // the epilogue needs NO barriers and overlaps the next tile's staging.
-  constexpr int TB = BM * NKK * 32 * 2;  // one staged tile
+  constexpr int TB = TILE_BYTES;  // one staged tile
   __shared__ char smem[2 * TB * 2 + 2 * BM * KMAX * 8];
   char* const smem0 = smem;  // avoid static-init addrspacecast of arrays
   auto abuf = [&](int i) -> char* { return smem0 + i * TB; };
@@ -293,7 +219,7 @@ __global__ __launch_bounds__(THREADS, 4 - NKK) void cosine_topk_partial_t(
   const int ntiles_total = (N + BN - 1) / BN;
   const int tile0 = chunk_id * chunk_tiles;
   const int tiles_here = min(chunk_tiles, ntiles_total - tile0);
-  const int nkt = D / (NKK * 32);
+  const int nkt = D / BK;
 
   // init lists (-inf scores; slot 0 is the min by construction)
   for (int i = tid; i < 2 * BM * KMAX; i += THREADS) {
@@ -310,9 +236,9 @@ __global__ __launch_bounds__(THREADS, 4 - NKK) void cosine_topk_partial_t(
   __syncthreads();
   int cur = 0;
 
-  // EPI_MODE 7: per-row pruning threshold cached in a register. Lane l of
-  // each wave owns max(list-min, warm) for row wr*64+l of col-half wc, so
-  // the pre-check needs no LDS reads at all (the volatile list reads at
+  // REG_THR: per-row pruning threshold cached in a register. Lane
+  // l of each wave owns max(list-min, warm) for row wr*64+l of col-half wc,
+  // so the pre-check needs no LDS reads at all (the volatile list reads at
   // the 16 unrolled call boundaries otherwise serialize ~70 lgkmcnt(0)
   // waits per tile per wave — measured 650 vs 884 TF full-vs-precheck).
   float rmin_reg = NEG_INF;
@@ -327,8 +253,7 @@ __global__ __launch_bounds__(THREADS, 4 - NKK) void cosine_topk_partial_t(
     float warm = NEG_INF;
     if (EPI_MODE != 1 && rowthr != nullptr && row0 + wr * 64 + lane < B)
       warm = dec_f32(rowthr[row0 + wr * 64 + lane]);
-    if constexpr (EPI_MODE >= 7 && EPI_MODE <= 12)
-      rmin_reg = fmaxf(rmin_reg, warm);
+    if constexpr (REG_THR) rmin_reg = fmaxf(rmin_reg, warm);
 
     f32x4 acc[4][4];
 #pragma unroll
@@ -341,34 +266,29 @@ __global__ __launch_bounds__(THREADS, 4 - NKK) void cosine_topk_partial_t(
       // tile j+1's first K-tile, so the epilogue below runs while that
       // staging is in flight.
       if (kt + 1 < nkt) {
-        const int kb = (kt + 1) * NKK * 64;
-        stage_tile_n<NKK>(Q, row0, B - 1, qrow_bytes, kb, abuf(cur ^ 1), wid, lane);
-        stage_tile_n<NKK>(C, col0, N - 1, qrow_bytes, kb, bbuf(cur ^ 1), wid, lane);
+        const int kb = (kt + 1) * BK * 2;
+        stage_tile(Q, row0, B - 1, qrow_bytes, kb, abuf(cur ^ 1), wid, lane);
+        stage_tile(C, col0, N - 1, qrow_bytes, kb, bbuf(cur ^ 1), wid, lane);
       } else if (j + 1 < tiles_here) {
-        stage_tile_n<NKK>(Q, row0, B - 1, qrow_bytes, 0, abuf(cur ^ 1), wid, lane);
-        stage_tile_n<NKK>(C, col0 + BN, N - 1, qrow_bytes, 0, bbuf(cur ^ 1), wid, lane);
+        stage_tile(Q, row0, B - 1, qrow_bytes, 0, abuf(cur ^ 1), wid, lane);
+        stage_tile(C, col0 + BN, N - 1, qrow_bytes, 0, bbuf(cur ^ 1), wid, lane);
       }
 #pragma unroll
-      for (int kk = 0; kk < NKK; ++kk) {
+      for (int kk = 0; kk < BK / 32; ++kk) {
         bf16x8 afrag[4], bfrag[4];
         const int slot = kk * 4 + g;
 #pragma unroll
         for (int m = 0; m < 4; ++m)
-          afrag[m] = read_frag_n<NKK>(abuf(cur), wr * 64 + m * 16 + cl, slot);
+          afrag[m] = read_frag(abuf(cur), wr * 64 + m * 16 + cl, slot);
 #pragma unroll
         for (int n = 0; n < 4; ++n)
-          bfrag[n] = read_frag_n<NKK>(bbuf(cur), wc * 64 + n * 16 + cl, slot);
-        // EPI_MODE 12 experiment: raise wave priority through the MFMA
-        // burst (8p-style s_setprio) so the co-resident wave's VALU work
-        // interleaves under it
-        if constexpr (EPI_MODE == 12) __builtin_amdgcn_s_setprio(1);
+          bfrag[n] = read_frag(bbuf(cur), wc * 64 + n * 16 + cl, slot);
 #pragma unroll
         for (int m = 0; m < 4; ++m)
 #pragma unroll
           for (int n = 0; n < 4; ++n)
             acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
                 afrag[m], bfrag[n], acc[m][n], 0, 0, 0);
-        if constexpr (EPI_MODE == 12) __builtin_amdgcn_s_setprio(0);
       }
       if (kt + 1 < nkt) {
         __syncthreads();  // drains prefetch glds; guards buffer reuse
@@ -391,28 +311,6 @@ __global__ __launch_bounds__(THREADS, 4 - NKK) void cosine_topk_partial_t(
 #pragma unroll
         for (int n = 0; n < 4; ++n)
           asm volatile("" ::"v"(acc[m][n]));
-    } else if constexpr (EPI_MODE == 7) {
-      // pre-check only here (registers + cross-lane ops, no LDS, no
-      // calls); qualifying (m,reg) groups set a bit and extract after
-      // the tile barrier below, where vmcnt is naturally drained so the
-      // noinline callee's conservative entry wait costs nothing.
-      const int colb = col0 + wc * 64 + cl;
-#pragma unroll
-      for (int m = 0; m < 4; ++m) {
-#pragma unroll
-        for (int reg = 0; reg < 4; ++reg) {
-          const float rwall = __shfl(rmin_reg, m * 16 + g * 4 + reg, 64);
-          float w0 = (colb + 0 < N) ? acc[m][0][reg] : NEG_INF;
-          float w1 = (colb + 16 < N) ? acc[m][1][reg] : NEG_INF;
-          float w2 = (colb + 32 < N) ? acc[m][2][reg] : NEG_INF;
-          float w3 = (colb + 48 < N) ? acc[m][3][reg] : NEG_INF;
-          float gmax = fmaxf(fmaxf(w0, w1), fmaxf(w2, w3));
-#pragma unroll
-          for (int off = 1; off < 16; off <<= 1)
-            gmax = fmaxf(gmax, __shfl_xor(gmax, off, 64));
-          if (gmax > rwall) qmask |= 1u << (m * 4 + reg);
-        }
-      }
     } else {
       const int colb = col0 + wc * 64 + cl;
 #pragma unroll
@@ -421,12 +319,12 @@ __global__ __launch_bounds__(THREADS, 4 - NKK) void cosine_topk_partial_t(
         for (int reg = 0; reg < 4; ++reg) {
           const int row = wr * 64 + m * 16 + g * 4 + reg;
           const int lbase = (wc * BM + row) * KMAX;
-          // EPI_MODE 8 reads the per-row threshold from the register
+          // REG_THR reads the per-row threshold from the register
           // cache (one cross-lane shuffle) instead of a volatile LDS
           // read; the 16 unrolled call-boundary reads otherwise cost
           // ~70 serialized lgkmcnt(0) waits per tile per wave.
           float rwarm, rmin0;
-          if constexpr (EPI_MODE >= 8 && EPI_MODE <= 11) {
+          if constexpr (REG_THR) {
             rwarm = __shfl(rmin_reg, m * 16 + g * 4 + reg, 64);
             rmin0 = rwarm;
           } else {
@@ -437,12 +335,12 @@ __global__ __launch_bounds__(THREADS, 4 - NKK) void cosine_topk_partial_t(
           float w1 = (colb + 16 < N) ? acc[m][1][reg] : NEG_INF;
           float w2 = (colb + 32 < N) ? acc[m][2][reg] : NEG_INF;
           float w3 = (colb + 48 < N) ? acc[m][3][reg] : NEG_INF;
-          // EPI_MODE 11: one ballot replaces the 4-deep shfl_xor max
+          // BALLOT_CHECK: one ballot replaces the 4-deep shfl_xor max
           // reduce in the pre-check (same predicate: does ANY lane of
           // the group beat the threshold) — halves the cross-lane
           // dependency chain of the hot no-candidate path.
           bool qual;
-          if constexpr (EPI_MODE == 11 || EPI_MODE == 12) {
+          if constexpr (BALLOT_CHECK) {
             const float lmax = fmaxf(fmaxf(w0, w1), fmaxf(w2, w3));
             qual = (__ballot(lmax > rmin0) & (0xFFFFull << (g * 16))) != 0;
           } else {
@@ -453,9 +351,6 @@ __global__ __launch_bounds__(THREADS, 4 - NKK) void cosine_topk_partial_t(
             qual = gmax > rmin0;
           }
           if (qual) {
-            if constexpr (EPI_MODE == 3) {
-              if (cl == 0 && stats) atomicAdd(&stats[0], 1ull);
-            }
             if constexpr (EPI_MODE == 4) {
               // k=1: group argmax, leader max-merges into list slot 0
               float b = w0;
@@ -475,28 +370,7 @@ __global__ __launch_bounds__(THREADS, 4 - NKK) void cosine_topk_partial_t(
                 lsc[lbase] = mv;
                 lix[lbase] = colb + bn * 16;
               }
-            } else if constexpr (EPI_MODE == 6) {
-              topk_extract_group_bl<true>(lsc, lix, lbase, rwarm, w0, w1,
-                                          w2, w3, colb, N, lane, g, rowthr,
-                                          (row0 + row < B) ? row0 + row + 1 : 0);
-            } else if constexpr (EPI_MODE >= 9 && EPI_MODE <= 12) {
-              // EPI_MODE 10: during list bootstrap (no threshold yet)
-              // the inline insert would almost always fall through to
-              // the callee anyway — skip straight to it. (A flag, not a
-              // goto: a goto would block loop unrolling and trip the
-              // runtime-indexed-accumulator scratch path.)
-              bool storm = false;
-              if constexpr (EPI_MODE == 10) {
-                if (rwarm <= NEG_INF) {
-                  storm = true;
-                  topk_extract_group<true>(lsc, lix, lbase, rwarm, w0, w1,
-                                           w2, w3, colb, N, lane, g, rowthr,
-                                           (row0 + row < B) ? row0 + row + 1
-                                                            : 0);
-                  qmask = 1;
-                }
-              }
-              if (!storm) {
+            } else if constexpr (INLINE_INSERT) {
               // inline single-insert fast path: the group argmax leader
               // inserts directly (no call, so no callee-entry
               // s_waitcnt vmcnt(0) draining the staging stream); only
@@ -546,7 +420,7 @@ __global__ __launch_bounds__(THREADS, 4 - NKK) void cosine_topk_partial_t(
               const float nmb = fmaxf(__shfl(nmn, mlane, 64), rwarm);
               const float g2l = fmaxf(fmaxf(w0, w1), fmaxf(w2, w3));
               bool more;
-              if constexpr (EPI_MODE == 11 || EPI_MODE == 12) {
+              if constexpr (BALLOT_CHECK) {
                 more = (__ballot(g2l > nmb) & (0xFFFFull << (g * 16))) != 0;
               } else {
                 float g2 = g2l;
@@ -559,8 +433,7 @@ __global__ __launch_bounds__(THREADS, 4 - NKK) void cosine_topk_partial_t(
                 topk_extract_group<true>(lsc, lix, lbase, rwarm, w0, w1, w2,
                                          w3, colb, N, lane, g, rowthr,
                                          (row0 + row < B) ? row0 + row + 1 : 0);
-              }
-            } else if constexpr (EPI_MODE != 2) {
+            } else {
               topk_extract_group<true>(lsc, lix, lbase, rwarm, w0, w1, w2,
                                        w3, colb, N, lane, g, rowthr,
                                        (row0 + row < B) ? row0 + row + 1 : 0);
@@ -571,46 +444,14 @@ __global__ __launch_bounds__(THREADS, 4 - NKK) void cosine_topk_partial_t(
       }
       // refresh the register threshold cache from the settled list minima
       // (wave-local: one coalesced LDS read per lane, before the barrier)
-      if constexpr (EPI_MODE >= 8 && EPI_MODE <= 12) {
+      if constexpr (REG_THR) {
         if (__any(qmask != 0))
           rmin_reg = fmaxf(rmin_reg, lsc[(wc * BM + wr * 64 + lane) * KMAX]);
       }
     }
     __syncthreads();  // next tile's first K-tile staged; lists settled
     cur ^= 1;
-
-    if constexpr (EPI_MODE == 7) {
-      // deferred extraction: prefetch for tile j+1 has completed at the
-      // barrier above, so the callee's entry s_waitcnt vmcnt(0) is free
-      // and the glds stream it would otherwise drain is untouched.
-      if (__any(qmask != 0)) {
-        const int colb = col0 + wc * 64 + cl;
-#pragma unroll
-        for (int m = 0; m < 4; ++m) {
-#pragma unroll
-          for (int reg = 0; reg < 4; ++reg) {
-            if (qmask & (1u << (m * 4 + reg))) {
-              const int row = wr * 64 + m * 16 + g * 4 + reg;
-              const int lbase = (wc * BM + row) * KMAX;
-              const float rwall = __shfl(rmin_reg, m * 16 + g * 4 + reg, 64);
-              float w0 = (colb + 0 < N) ? acc[m][0][reg] : NEG_INF;
-              float w1 = (colb + 16 < N) ? acc[m][1][reg] : NEG_INF;
-              float w2 = (colb + 32 < N) ? acc[m][2][reg] : NEG_INF;
-              float w3 = (colb + 48 < N) ? acc[m][3][reg] : NEG_INF;
-              topk_extract_group<true>(lsc, lix, lbase, rwall, w0, w1, w2,
-                                       w3, colb, N, lane, g, rowthr,
-                                       (row0 + row < B) ? row0 + row + 1 : 0);
-            }
-          }
-        }
-        // refresh the register threshold from the settled list minima
-        // (slot 0 is each list's min): one coalesced LDS read per lane.
-        rmin_reg = fmaxf(rmin_reg, lsc[(wc * BM + wr * 64 + lane) * KMAX]);
-      }
-    }
   }
-
-  if constexpr (EPI_MODE == 7) __syncthreads();  // deferred lists settled
 
   // write partials: [B][nchunks][KMAX]; merge the two col-half lists
   if (tid < BM) {
@@ -648,9 +489,6 @@ __global__ __launch_bounds__(THREADS, 4 - NKK) void cosine_topk_partial_t(
   }
 }
 
-inline constexpr auto cosine_topk_partial = cosine_topk_partial_t<0, 2>;
-
-
 // ===========================================================================
 // 256x256-tile 8-phase counted-pipeline kernel (guide T3+T4+T5).
 //
@@ -681,64 +519,20 @@ inline constexpr auto cosine_topk_partial = cosine_topk_partial_t<0, 2>;
 // ===========================================================================
 
 
-constexpr int BM8 = 256;
-constexpr int BN8 = 256;
 constexpr int THREADS8 = 512;
 constexpr int HALF8 = 16384;  // one [128][64] bf16 half-image
 constexpr int EGCAP = 8;          // emission stash slots per (block, wave)
 constexpr int ESTASH_STRIDE = 64 + EGCAP * 1024;  // meta + slots, bytes
 
-
-
-// EPI_MODE: 0 = stash+drain epilogue, 1 = GEMM only, 5 = slab-deferred
-// epilogue (acc quadrants stream to a per-block global slab at tile end;
-// the NEXT tile's windows drain one 32-col slice each, so the top-k
-// maintenance hides under the MFMA pipeline instead of being exposed
-// after the last window), 6 = ballot-skip stash (a register ballot
-// pre-check against the rowthr floors marks which waves have ANY
-// qualifying candidate this tile; unflagged waves' stash+drain phases
-// are skipped uniformly — best 8p variant: 686 TF vs 420 for mode 0),
-// 7 = per-row LDS candidate queue + single drain with the stash loop
-// kept for bootstrap/overflow repair (correct but spills ~490 B/lane:
-// the accumulators must stay live across the repair path — see
-// profiles/knn_kernel_history.md for why a queue-only version was
-// abandoned at the 256-VGPR/2-wave cap).
-// Rare-path drain for the emission epilogue (EPI_MODE 9): the cold path
+// Rare-path drain for the emission epilogue (EPI_MODE 9/15): the cold path
 // stashes qualifying groups' accumulator quads into the wave's private
-// slice of the dead A-image (plain LDS stores, no calls while the 128
-// accumulator VGPRs are live), then makes ONE call here per wave per
+// slice of the global emission scratch (plain stores, no calls while the
+// 128 accumulator VGPRs are live), then makes ONE call here per wave per
 // cold tile. By call time the accumulators are dead, so the call costs
 // no spills — earlier structures (per-group callee: 32-reg/tile
 // pre-spill; inlined appends: 0.5-1 KiB/lane scratch) all lost to the
 // acc-liveness-across-append problem. __noinline__ keeps the body out
 // of the sweep's register allocation entirely.
-// v3-era per-group append callee, kept for A/B isolation (EPI_MODE 14):
-// calls it once per qualifying group with the accumulators still live.
-__device__ __noinline__ void emit_candidates(
-    unsigned long long* __restrict__ cand, unsigned* __restrict__ ccount,
-    long ccap, int grow, float v0, float v1, float v2, float v3, int colb,
-    int N, float thr) {
-  const bool q0 = v0 >= thr && colb < N;
-  const bool q1 = v1 >= thr && colb + 16 < N;
-  const bool q2 = v2 >= thr && colb + 32 < N;
-  const bool q3 = v3 >= thr && colb + 48 < N;
-  const int myc = (int)q0 + (int)q1 + (int)q2 + (int)q3;
-  if (!myc) return;
-  unsigned pos = atomicAdd(&ccount[grow], (unsigned)myc);
-  unsigned long long* crow = cand + (size_t)grow * ccap;
-#pragma unroll
-  for (int n = 0; n < 4; ++n) {
-    const bool qn = n == 0 ? q0 : n == 1 ? q1 : n == 2 ? q2 : q3;
-    const float vn = n == 0 ? v0 : n == 1 ? v1 : n == 2 ? v2 : v3;
-    if (qn) {
-      if (pos < (unsigned)ccap)
-        crow[pos] = ((unsigned long long)enc_f32(vn) << 32) |
-                    (unsigned)(0x7fffffff - (colb + n * 16));
-      ++pos;
-    }
-  }
-}
-
 __device__ __noinline__ void emit_stashed(
     unsigned long long* __restrict__ cand, unsigned* __restrict__ ccount,
     long ccap, char* stash, int ng, int rowbase, int colb, int N, int B,
@@ -773,6 +567,19 @@ __device__ __noinline__ void emit_stashed(
   }
 }
 
+// EPI_MODE (numbering is historical; the pruned variants and their
+// verdicts are in profiles/knn_kernel_history.md):
+//   1  GEMM only (probe8p, tools/knn_probe.hip)
+//   6  ballot-skip stash+drain into shared per-row lists: a register
+//      ballot pre-check against the rowthr floors marks which waves have
+//      ANY qualifying candidate this tile; unflagged waves' stash+drain
+//      phases are skipped uniformly (KAKVEDA_KNN_KERNEL=8pbl, 686 TF)
+//   9  threshold emission — the PRODUCTION DEFAULT at N >= 64k: no lists,
+//      scores >= the prepass floor go to a global candidate buffer
+//   12 = 9's hot sweep with the cold path compiled out (probe8p)
+//   15 = 9 with block-lifetime packed threshold vectors (=8pe2)
+// `stats` and `slab` are unused (they belonged to pruned modes) and stay
+// in the signature so kernel symbols and kernarg offsets do not move.
 template <int EPI_MODE>
 __global__ __launch_bounds__(THREADS8, 2) void cosine_topk_partial8p_t(
     const bf16_t* __restrict__ Q, const bf16_t* __restrict__ C,
@@ -783,7 +590,8 @@ __global__ __launch_bounds__(THREADS8, 2) void cosine_topk_partial8p_t(
     unsigned long long* __restrict__ cand = nullptr,
     unsigned* __restrict__ ccount = nullptr, long ccap = 0,
     char* __restrict__ estash = nullptr) {
-  __shared__ char smem[8 * HALF8 + 2 * BM8 * KMAX * 4 + 32 + BM8 * 4 + 32];
+  constexpr bool EMIT = EPI_MODE == 9 || EPI_MODE == 12 || EPI_MODE == 15;
+  __shared__ char smem[8 * HALF8 + 2 * BM8 * KMAX * 4 + 32];
   char* const smem0 = smem;
   // buffer b in {0,1}: A half h at b*4*HALF8 + h*HALF8; B half h at +2*HALF8
   auto ahalf = [&](int b, int h) -> char* {
@@ -795,9 +603,6 @@ __global__ __launch_bounds__(THREADS8, 2) void cosine_topk_partial8p_t(
   float* lsc = (float*)(smem + 8 * HALF8);
   int* lix = (int*)(smem + 8 * HALF8 + BM8 * KMAX * 4);
   int* wflags = (int*)(smem + 8 * HALF8 + 2 * BM8 * KMAX * 4);
-  int* ccnt = (int*)(smem + 8 * HALF8 + 2 * BM8 * KMAX * 4 + 32);
-  unsigned* covf =
-      (unsigned*)(smem + 8 * HALF8 + 2 * BM8 * KMAX * 4 + 32 + BM8 * 4);
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -931,74 +736,13 @@ __global__ __launch_bounds__(THREADS8, 2) void cosine_topk_partial8p_t(
       }
   }
 
-  // slab-deferred epilogue state (EPI_MODE 5): this block's 256 KiB slab.
-  // Thread tid<256 owns list row tid; its warm threshold is cached in a
-  // register per tile. The drain is array-free (slot 0 of a list always
-  // holds its min, so the running threshold is one LDS read) to keep the
-  // in-window register footprint tiny next to the 128-reg accumulator.
-  float* myslab = nullptr;
-  if constexpr (EPI_MODE == 5) {
-    const long bid_flat = blockIdx.x + (long)gridDim.x * blockIdx.y;
-    myslab = slab + bid_flat * (BM8 * BN8);
-  }
-  auto drain_slice = [&](int prev_col0, int w, float warm_r) {
-    if (tid >= BM8) return;
-    const int row = tid;
-    volatile float* lrow = lsc + row * KMAX;
-    volatile int* irow = lix + row * KMAX;
-    float rmin = fmaxf(lrow[0], warm_r);  // slot 0 is the list min
-    const float* srow = myslab + row * BN8 + w * 32;
-    bool dirty = false;
-    float mn_out = 0.f;
-#pragma unroll 2
-    for (int ii = 0; ii < 8; ++ii) {
-      const float4 v4 = *(const float4*)(srow + 4 * ii);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const float v = e == 0 ? v4.x : e == 1 ? v4.y : e == 2 ? v4.z : v4.w;
-        const int gc = prev_col0 + w * 32 + 4 * ii + e;
-        if (v > rmin && gc < N) {
-          // replace slot 0 (the min) with v, then restore the invariant
-          float mn2 = 1e38f;
-          int m2 = 0;
-#pragma unroll
-          for (int q = 1; q < KMAX; ++q) {
-            const float s = lrow[q];
-            if (s < mn2) { mn2 = s; m2 = q; }
-          }
-          if (v <= mn2) {
-            lrow[0] = v;
-            irow[0] = gc;
-          } else {
-            lrow[0] = mn2;
-            irow[0] = irow[m2];
-            lrow[m2] = v;
-            irow[m2] = gc;
-          }
-          const float nmn = fminf(mn2, v);
-          rmin = fmaxf(rmin, nmn);
-          mn_out = nmn;
-          dirty = true;
-        }
-      }
-    }
-    if (dirty && rowthr != nullptr && mn_out > NEG_INF && row0 + row < B)
-      atomicMax(&rowthr[row0 + row], enc_f32(mn_out));
-  };
-
   for (int j = 0; j < tiles_here; ++j) {
     const int col0 = (tile0 + j) * BN8;
 
-    float warm5 = NEG_INF;
-    if constexpr (EPI_MODE == 5) {
-      if (rowthr != nullptr && tid < BM8 && row0 + tid < B)
-        warm5 = dec_f32(rowthr[row0 + tid]);
-    }
-    // EPI_MODE 6/7/9: per-lane threshold floors for this wave-half's two
-    // rows (rows beyond B get +inf so clamped-row garbage never flags)
+    // per-lane threshold floors for this wave-half's two rows (rows
+    // beyond B get +inf so clamped-row garbage never flags)
     float thr0 = NEG_INF, thr1 = NEG_INF;
-    if constexpr (EPI_MODE == 6 || EPI_MODE == 7 || EPI_MODE == 9 ||
-                  EPI_MODE == 12 || EPI_MODE == 14 || EPI_MODE == 15) {
+    if constexpr (EPI_MODE != 1) {
       const int r0g = row0 + wr * 128 + lane;
       thr0 = (r0g < B) ? (rowthr ? dec_f32(rowthr[r0g]) : NEG_INF) : 1e38f;
       thr1 = (r0g + 64 < B) ? (rowthr ? dec_f32(rowthr[r0g + 64]) : NEG_INF)
@@ -1071,36 +815,16 @@ __global__ __launch_bounds__(THREADS8, 2) void cosine_topk_partial8p_t(
         __builtin_amdgcn_s_setprio(0);
         __builtin_amdgcn_s_barrier();  // read-retirement vs next glds
       }
-      if constexpr (EPI_MODE == 5) {
-        // drain one slice of the previous tile's slab under this window's
-        // pipeline (slab stores were separated by >= one window of
-        // barriers; same workgroup -> L1-visible)
-        if (j > 0 && kt < 8) drain_slice(col0 - BN8, kt, warm5);
-      }
     }
 
     // ---- top-k epilogue ---------------------------------------------------
-    if constexpr (EPI_MODE == 5) {
-      // stream the final accumulators to the block's slab; the next tile's
-      // windows (or the post-loop flush) merge them into the lists
-#pragma unroll
-      for (int m = 0; m < 8; ++m)
-#pragma unroll
-        for (int n = 0; n < 4; ++n)
-#pragma unroll
-          for (int reg = 0; reg < 4; ++reg)
-            myslab[(wr * 128 + m * 16 + g * 4 + reg) * BN8 + wc * 64 +
-                   n * 16 + cl] = acc[m][n][reg];
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // slab stores done
-      __builtin_amdgcn_s_barrier();
-    } else if constexpr (EPI_MODE == 1) {
+    if constexpr (EPI_MODE == 1) {
 #pragma unroll
       for (int m = 0; m < 8; ++m)
 #pragma unroll
         for (int n = 0; n < 4; ++n)
           asm volatile("" ::"v"(acc[m][n]));
-    } else if constexpr (EPI_MODE == 9 || EPI_MODE == 12 || EPI_MODE == 14 ||
-                         EPI_MODE == 15) {
+    } else if constexpr (EMIT) {
       // ---- threshold-emission epilogue (round 2): no lists, no stash
       // phases, no barriers — the 1017 TF GEMM core's full accumulator
       // sweep is a register compare + rare global append. Exactness: the
@@ -1117,9 +841,9 @@ __global__ __launch_bounds__(THREADS8, 2) void cosine_topk_partial8p_t(
       // unspilled (a single-pass sweep with per-group calls pre-spilled
       // 32 regs per tile per wave -> ~27 GB of scratch traffic at the
       // 10M bench, the measured 917-vs-1017 TF gap). The COLD pass
-      // (wave-uniform qmask != 0, ~12% of tiles per wave) re-derives the
-      // thresholds and makes the rare __noinline__ emit_candidates
-      // calls; its spills live in that cold block only.
+      // (wave-uniform qmask != 0, ~12% of tiles per wave) stashes the
+      // qualifying groups and makes the rare __noinline__ emit_stashed
+      // call; its spills live in that cold block only.
       const int colb = col0 + wc * 64 + cl;
       unsigned qm32 = 0;
       if constexpr (EPI_MODE == 15) {
@@ -1170,33 +894,12 @@ __global__ __launch_bounds__(THREADS8, 2) void cosine_topk_partial8p_t(
         // probe-only: hot sweep computed, cold path compiled out — lets
         // the host isolate the sweep's cost from the emission cost
         asm volatile("" ::"s"(qm32));
-      } else if constexpr (EPI_MODE == 14) {
-        // isolation A/B: the v3-era cold path (per-group callee with the
-        // accumulators live; pays the pre-spill, no stash, no barrier)
-        if (__builtin_expect(qm32 != 0, 0)) {
-#pragma unroll
-          for (int m = 0; m < 8; ++m) {
-#pragma unroll
-            for (int reg = 0; reg < 4; ++reg) {
-              if (!(qm32 & (1u << (m * 4 + reg)))) continue;
-              const int rl = m * 16 + g * 4 + reg;
-              const float thr = __shfl(m >= 4 ? thr1 : thr0, rl & 63, 64);
-              const float gmax = fmaxf(fmaxf(acc[m][0][reg], acc[m][1][reg]),
-                                       fmaxf(acc[m][2][reg], acc[m][3][reg]));
-              const int grow = row0 + wr * 128 + rl;
-              if (gmax >= thr && grow < B)
-                emit_candidates(cand, ccount, ccap, grow, acc[m][0][reg],
-                                acc[m][1][reg], acc[m][2][reg],
-                                acc[m][3][reg], colb, N, thr);
-            }
-          }
-        }
       } else {
         if (__builtin_expect(qm32 != 0, 0)) {  // uniform cold path
           // stash qualifying groups into this (block, wave)'s private
           // slice of the GLOBAL emission scratch. An LDS stash in the
           // "dead" last-window A-image corrupted later tiles' scores
-          // (isolated by the mode-14 A/B: v3 clean, LDS-stash dirty —
+          // (isolated by an A/B against a stash-free cold path —
           // the image interacts with the cross-tile staging pipeline in
           // a way the stash-phase epilogues' barrier discipline tolerates
           // but a late per-wave write does not); global scratch has no
@@ -1238,134 +941,25 @@ __global__ __launch_bounds__(THREADS8, 2) void cosine_topk_partial8p_t(
         }
       }
     } else {
-      // ---- EPI_MODE 6/7 pre-check: one register ballot per (m,reg)
-      // row group against the rowthr floors; waves with no qualifying
+      // ---- EPI_MODE 6 pre-check: one register ballot per (m,reg) row
+      // group against the rowthr floors; waves with no qualifying
       // candidate skip their stash+drain phase below (uniformly — the
       // flags live in LDS so every wave takes the same branch).
-      bool boot = true;        // stash phases process every row
-      bool run_phases = true;  // whether the stash loop runs at all
-      unsigned qual = 0;       // per-(m,reg) qualifying bits (my groups)
-      (void)boot;
-      (void)run_phases;
-      if constexpr (EPI_MODE == 6 || EPI_MODE == 7) {
-        if constexpr (EPI_MODE == 7) {
-          for (int i = tid; i < BM8; i += THREADS8) ccnt[i] = 0;
-          if (tid < 8) covf[tid] = 0;
-        }
+      unsigned qual = 0;  // per-(m,reg) qualifying bits (my groups)
 #pragma unroll
-        for (int m = 0; m < 8; ++m) {
+      for (int m = 0; m < 8; ++m) {
 #pragma unroll
-          for (int reg = 0; reg < 4; ++reg) {
-            const int rl = m * 16 + g * 4 + reg;  // 0..127 within half
-            const float thr = __shfl(m >= 4 ? thr1 : thr0, rl & 63, 64);
-            const float lmax =
-                fmaxf(fmaxf(acc[m][0][reg], acc[m][1][reg]),
-                      fmaxf(acc[m][2][reg], acc[m][3][reg]));
-            if (__ballot(lmax > thr) & (0xFFFFull << (g * 16)))
-              qual |= 1u << (m * 4 + reg);
-          }
-        }
-        if (lane == 0) wflags[wid] = __any(qual != 0) ? 1 : 0;
-        __syncthreads();  // flags + queue counters visible
-      }
-      if constexpr (EPI_MODE == 7) {
-        // EPI_MODE 7: one-pass LDS candidate queue. Qualifying lanes
-        // append (score, col) to their row's slot array; one thread per
-        // row folds them into the shared list. The 8-phase stash loop
-        // runs only for bootstrap tiles (most waves flagged: thresholds
-        // not yet established) and for rows whose queue overflowed —
-        // steady state pays 3 barriers/tile instead of 16.
-        constexpr int CQ8 = 8;
-        const int t_last7 = j * nkt + nkt - 1;
-        float* csc = (float*)ahalf(t_last7 & 1, 0);    // [256][CQ8]
-        int* ccol = (int*)(csc + BM8 * CQ8);           // [256][CQ8]
-        int nfl = 0;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) nfl += wflags[i];
-        boot = nfl >= 6;
-        run_phases = boot;
-        if (!boot) {
-          if (qual) {
-            const int colb = col0 + wc * 64 + cl;
-#pragma unroll
-            for (int m = 0; m < 8; ++m) {
-#pragma unroll
-              for (int reg = 0; reg < 4; ++reg) {
-                if (qual & (1u << (m * 4 + reg))) {
-                  const int row = wr * 128 + m * 16 + g * 4 + reg;
-                  const float thr =
-                      __shfl(m >= 4 ? thr1 : thr0,
-                             (m * 16 + g * 4 + reg) & 63, 64);
-#pragma unroll
-                  for (int n = 0; n < 4; ++n) {
-                    const float v = acc[m][n][reg];
-                    const int gc = colb + n * 16;
-                    if (v > thr && gc < N) {
-                      const int pos = atomicAdd(&ccnt[row], 1);
-                      if (pos < CQ8) {
-                        csc[row * CQ8 + pos] = v;
-                        ccol[row * CQ8 + pos] = gc;
-                      } else {
-                        atomicOr(&covf[row >> 5], 1u << (row & 31));
-                      }
-                    }
-                  }
-                }
-              }
-            }
-          }
-          __syncthreads();  // queue complete
-          if (tid < BM8) {
-            const int row = tid;
-            const int grow = row0 + row;
-            const bool ovf = (covf[row >> 5] >> (row & 31)) & 1;
-            int nq = ccnt[row];
-            if (nq > CQ8) nq = CQ8;
-            if (!ovf && nq > 0 && grow < B) {
-              // in-place LDS list update (slot 0 holds the min): no
-              // register arrays — acc (128 VGPRs) must stay live for
-              // the overflow stash pass, so the drain's footprint has
-              // to be tiny to avoid scratch spill.
-              volatile float* lrow = lsc + row * KMAX;
-              volatile int* irow = lix + row * KMAX;
-              float rmin = lrow[0];
-              bool dirty = false;
-              float mn_out = NEG_INF;
-              for (int i = 0; i < nq; ++i) {
-                const float v = csc[row * CQ8 + i];
-                const int gc = ccol[row * CQ8 + i];
-                if (v > rmin) {
-                  float mn2 = 1e38f;
-                  int m2 = 0;
-#pragma unroll
-                  for (int q = 1; q < KMAX; ++q) {
-                    const float sq = lrow[q];
-                    if (sq < mn2) { mn2 = sq; m2 = q; }
-                  }
-                  if (v <= mn2) {
-                    lrow[0] = v;
-                    irow[0] = gc;
-                  } else {
-                    lrow[0] = mn2;
-                    irow[0] = irow[m2];
-                    lrow[m2] = v;
-                    irow[m2] = gc;
-                  }
-                  const float nmn = fminf(mn2, v);
-                  rmin = nmn;
-                  mn_out = nmn;
-                  dirty = true;
-                }
-              }
-              if (dirty && rowthr != nullptr && mn_out > NEG_INF)
-                atomicMax(&rowthr[grow], enc_f32(mn_out));
-            }
-          }
-          __syncthreads();  // lists settled; covf stable
-          run_phases = (covf[0] | covf[1] | covf[2] | covf[3] | covf[4] |
-                        covf[5] | covf[6] | covf[7]) != 0;
+        for (int reg = 0; reg < 4; ++reg) {
+          const int rl = m * 16 + g * 4 + reg;  // 0..127 within half
+          const float thr = __shfl(m >= 4 ? thr1 : thr0, rl & 63, 64);
+          const float lmax = fmaxf(fmaxf(acc[m][0][reg], acc[m][1][reg]),
+                                   fmaxf(acc[m][2][reg], acc[m][3][reg]));
+          if (__ballot(lmax > thr) & (0xFFFFull << (g * 16)))
+            qual |= 1u << (m * 4 + reg);
         }
       }
+      if (lane == 0) wflags[wid] = __any(qual != 0) ? 1 : 0;
+      __syncthreads();  // flags visible
       // ---- top-k epilogue (stash + lane-parallel register-list drain) --
       // The A images of the LAST window's buffer are dead during the
       // epilogue (A(t+2) staging is only issued at window t+1 phase 0),
@@ -1384,13 +978,8 @@ __global__ __launch_bounds__(THREADS8, 2) void cosine_topk_partial8p_t(
       float* stash = (float*)ahalf(t_last & 1, 0);
 #pragma unroll
       for (int phw = 0; phw < 8; ++phw) {
-        if constexpr (EPI_MODE == 7) {
-          if (!run_phases) break;  // uniform (LDS-derived)
-        }
-        if constexpr (EPI_MODE == 6 || EPI_MODE == 7) {
-          // stashing wave's wid = swr*4 + swc; uniform (flags in LDS)
-          if (!wflags[(phw & 1) * 4 + (phw >> 1)]) continue;
-        }
+        // stashing wave's wid = swr*4 + swc; uniform (flags in LDS)
+        if (!wflags[(phw & 1) * 4 + (phw >> 1)]) continue;
         const int swc = phw >> 1, swr = phw & 1;  // stashing wave
         if (wc == swc && wr == swr) {
 #pragma unroll
@@ -1405,80 +994,69 @@ __global__ __launch_bounds__(THREADS8, 2) void cosine_topk_partial8p_t(
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();  // stash visible to every wave
 
-        if constexpr (EPI_MODE != 2) {
-          if (lane < 16) {  // 8 waves x 16 lanes = one drainer per row
-            const int rl = wid * 16 + lane;         // 0..127 within half
-            const int row = swr * 128 + rl;
-            const int grow = row0 + row;
-            // mode 7: outside bootstrap, the stash pass only repairs
-            // rows whose candidate queue overflowed (queue-inserted
-            // rows are already exact; re-scanning them would be
-            // harmless but wasteful)
-            bool skip_row = false;
-            if constexpr (EPI_MODE == 7)
-              skip_row = !boot && !((covf[row >> 5] >> (row & 31)) & 1);
-            if (!skip_row) {
-            const int colq = col0 + swc * 64;
-            float ls[KMAX];
-            int li[KMAX];
+        if (lane < 16) {  // 8 waves x 16 lanes = one drainer per row
+          const int rl = wid * 16 + lane;         // 0..127 within half
+          const int row = swr * 128 + rl;
+          const int grow = row0 + row;
+          const int colq = col0 + swc * 64;
+          float ls[KMAX];
+          int li[KMAX];
+#pragma unroll
+          for (int q = 0; q < KMAX; ++q) {
+            ls[q] = lsc[row * KMAX + q];
+            li[q] = lix[row * KMAX + q];
+          }
+          float rmin = ls[0];
+#pragma unroll
+          for (int q = 1; q < KMAX; ++q) rmin = fminf(rmin, ls[q]);
+          if (rowthr != nullptr && grow < B)
+            rmin = fmaxf(rmin, dec_f32(rowthr[grow]));
+          bool dirty = false;
+          const float* srow = stash + rl * 64;
+#pragma unroll 4
+          for (int ii = 0; ii < 16; ++ii) {
+            const int iv = (ii + rl) & 15;  // bank stagger across rows
+            const float4 v4 = *(const float4*)(srow + 4 * iv);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+              const float v = e == 0 ? v4.x : e == 1 ? v4.y : e == 2 ? v4.z : v4.w;
+              const int gc = colq + 4 * iv + e;
+              if (v > rmin && gc < N) {
+                int mp = 0;
+                float mn1 = ls[0], mn2 = 1e38f;
+#pragma unroll
+                for (int q = 1; q < KMAX; ++q) {
+                  if (ls[q] < mn1) { mn2 = mn1; mn1 = ls[q]; mp = q; }
+                  else if (ls[q] < mn2) { mn2 = ls[q]; }
+                }
+#pragma unroll
+                for (int q = 0; q < KMAX; ++q)
+                  if (q == mp) { ls[q] = v; li[q] = gc; }
+                rmin = fmaxf(rmin, fminf(mn2, v));
+                dirty = true;
+              }
+            }
+          }
+          if (dirty) {
+            int mp = 0;
+            float mn = ls[0];
+#pragma unroll
+            for (int q = 1; q < KMAX; ++q)
+              if (ls[q] < mn) { mn = ls[q]; mp = q; }
+            // swap the min into slot 0 (list invariant), then write back
+            const float s_mp = ls[mp];
+            const int i_mp = li[mp];
+            ls[mp] = ls[0];
+            li[mp] = li[0];
+            ls[0] = s_mp;
+            li[0] = i_mp;
 #pragma unroll
             for (int q = 0; q < KMAX; ++q) {
-              ls[q] = lsc[row * KMAX + q];
-              li[q] = lix[row * KMAX + q];
+              lsc[row * KMAX + q] = ls[q];
+              lix[row * KMAX + q] = li[q];
             }
-            float rmin = ls[0];
-#pragma unroll
-            for (int q = 1; q < KMAX; ++q) rmin = fminf(rmin, ls[q]);
-            if (rowthr != nullptr && grow < B)
-              rmin = fmaxf(rmin, dec_f32(rowthr[grow]));
-            bool dirty = false;
-            const float* srow = stash + rl * 64;
-#pragma unroll 4
-            for (int ii = 0; ii < 16; ++ii) {
-              const int iv = (ii + rl) & 15;  // bank stagger across rows
-              const float4 v4 = *(const float4*)(srow + 4 * iv);
-#pragma unroll
-              for (int e = 0; e < 4; ++e) {
-                const float v = e == 0 ? v4.x : e == 1 ? v4.y : e == 2 ? v4.z : v4.w;
-                const int gc = colq + 4 * iv + e;
-                if (v > rmin && gc < N) {
-                  int mp = 0;
-                  float mn1 = ls[0], mn2 = 1e38f;
-#pragma unroll
-                  for (int q = 1; q < KMAX; ++q) {
-                    if (ls[q] < mn1) { mn2 = mn1; mn1 = ls[q]; mp = q; }
-                    else if (ls[q] < mn2) { mn2 = ls[q]; }
-                  }
-#pragma unroll
-                  for (int q = 0; q < KMAX; ++q)
-                    if (q == mp) { ls[q] = v; li[q] = gc; }
-                  rmin = fmaxf(rmin, fminf(mn2, v));
-                  dirty = true;
-                }
-              }
-            }
-            if (dirty) {
-              int mp = 0;
-              float mn = ls[0];
-#pragma unroll
-              for (int q = 1; q < KMAX; ++q)
-                if (ls[q] < mn) { mn = ls[q]; mp = q; }
-              // swap the min into slot 0 (list invariant), then write back
-              const float s_mp = ls[mp];
-              const int i_mp = li[mp];
-              ls[mp] = ls[0];
-              li[mp] = li[0];
-              ls[0] = s_mp;
-              li[0] = i_mp;
-#pragma unroll
-              for (int q = 0; q < KMAX; ++q) {
-                lsc[row * KMAX + q] = ls[q];
-                lix[row * KMAX + q] = li[q];
-              }
-              if (rowthr != nullptr && mn > NEG_INF && grow < B)
-                atomicMax(&rowthr[grow], enc_f32(mn));
-            }
-            }
+            if (rowthr != nullptr && mn > NEG_INF && grow < B)
+              atomicMax(&rowthr[grow], enc_f32(mn));
           }
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -1491,19 +1069,10 @@ __global__ __launch_bounds__(THREADS8, 2) void cosine_topk_partial8p_t(
     }
   }
 
-  if constexpr (EPI_MODE == 5) {
-    if (tiles_here > 0) {
-      const int last_col0 = (tile0 + tiles_here - 1) * BN8;
-      float warmf = NEG_INF;
-      if (rowthr != nullptr && tid < BM8 && row0 + tid < B)
-        warmf = dec_f32(rowthr[row0 + tid]);
-      for (int w = 0; w < 8; ++w) drain_slice(last_col0, w, warmf);
-    }
-  }
-
   // write partials: [B][nchunks][KMAX] (emission modes have no lists —
-  // their results went straight to the candidate buffer)
-  if constexpr (EPI_MODE != 9 && EPI_MODE != 12 && EPI_MODE != 14) {
+  // their results went straight to the candidate buffer; mode 15 still
+  // writes its untouched -inf lists, which nothing reads)
+  if constexpr (EPI_MODE != 9 && EPI_MODE != 12) {
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
     if (tid < BM8) {

@@ -244,18 +244,21 @@ def test_k1_argmax_fast_path():
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("variant", ["eager", "fast", "rege", "8pbl", "8pe", "8pe2"])
+@pytest.mark.parametrize(
+    "variant", ["eager", "fast", "rege", "8pbl", "8pe", "8pe2", "list"]
+)
 def test_kernel_variants_match_default(variant):
     """Every KAKVEDA_KNN_KERNEL variant must produce the same top-k
     scores as the default ballot kernel (env is read once per process,
     so variants run in a subprocess). The emission variant (8pe) only
     engages at N >= 64k (it needs the prepass floors), so it gets a
-    bigger corpus."""
+    bigger corpus; so does `list`, which there compares the forced list
+    kernel against default emission."""
     import os
     import subprocess
     import sys
 
-    n = 131072 if variant in ("8pe", "8pe2") else 8192
+    n = 131072 if variant in ("8pe", "8pe2", "list") else 8192
     code = (
         "import torch\n"
         "from kakveda_amd import ops\n"
@@ -528,6 +531,78 @@ def test_smallb_v4_matches_default():
         assert r.returncode == 0, r.stderr[-1500:]
         outs[sel] = float(r.stdout.split("CSUM")[1].strip())
     assert abs(outs[None] - outs["2"]) < 1e-2, outs
+
+
+def test_emission_overflow_falls_back_exact():
+    """A candidate-buffer overflow on the emission path reruns the batch
+    through the list kernel and stays exact. KAKVEDA_KNN_EMIT_CAP=4 makes
+    the overflow certain without any fault: an emission floor is the
+    8th-best score of a corpus sample, so every row emits at least ~8
+    candidates and any count above 4 overflows. Covers the MFMA emission
+    kernel (B=130) and the streaming small-batch kernel (B=3), a second
+    call per shape (the fallback guard must not stick), and the list
+    kernel at N >= 64k, where production only reaches it this way. The
+    warning is printed once per process."""
+    import os
+    import subprocess
+    import sys
+
+    code = (
+        "import torch\n"
+        "from kakveda_amd import ops\n"
+        "N, D = 65600, 128\n"
+        "g = torch.Generator(device='cuda').manual_seed(21)\n"
+        "c = torch.randn(N, D, generator=g, device='cuda')\n"
+        "c = (c / c.norm(dim=-1, keepdim=True)).to(torch.bfloat16)\n"
+        "for B in (130, 3):\n"
+        "    q = torch.randn(B, D, generator=g, device='cuda')\n"
+        "    q = (q / q.norm(dim=-1, keepdim=True)).to(torch.bfloat16)\n"
+        "    sims = q.float() @ c.float().t()\n"
+        "    rs, _ = torch.topk(sims, 5, dim=1)\n"
+        "    for call in range(2):\n"
+        "        s, i = ops.cosine_topk(q, c, 5)\n"
+        "        torch.cuda.synchronize()\n"
+        "        assert (i >= 0).all() and (i < N).all(), (B, call)\n"
+        "        assert torch.allclose(sims.gather(1, i), rs, atol=1e-4), (B, call)\n"
+        "        assert torch.allclose(s, rs, atol=2e-2, rtol=1e-2), (B, call)\n"
+        "print('OKFALLBACK')\n"
+    )
+    env = dict(os.environ)
+    env.pop("KAKVEDA_KNN_KERNEL", None)
+    env.pop("KAKVEDA_SMALLB", None)
+    env["KAKVEDA_KNN_EMIT_CAP"] = "4"
+    r = subprocess.run([sys.executable, "-c", code], env=env,
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert "OKFALLBACK" in r.stdout
+    assert r.stderr.count("emission candidate overflow") == 1, r.stderr[-2000:]
+
+
+def test_knn_kernel_env_rejected():
+    """An unrecognised KAKVEDA_KNN_KERNEL (here a removed variant name)
+    is an error that lists the accepted names, raised before any kernel
+    is launched — not a silent switch to the list kernel."""
+    import os
+    import subprocess
+    import sys
+
+    code = (
+        "import torch\n"
+        "from kakveda_amd import ops\n"
+        "q = torch.randn(8, 64, device='cuda').to(torch.bfloat16)\n"
+        "c = torch.randn(100, 64, device='cuda').to(torch.bfloat16)\n"
+        "try:\n"
+        "    ops.cosine_topk(q, c, 5)\n"
+        "except RuntimeError as exc:\n"
+        "    assert '8pe' in str(exc) and 'list' in str(exc), str(exc)\n"
+        "    print('OKREJECTED')\n"
+    )
+    env = dict(os.environ)
+    env["KAKVEDA_KNN_KERNEL"] = "dfr"
+    r = subprocess.run([sys.executable, "-c", code], env=env,
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert "OKREJECTED" in r.stdout
 
 
 @pytest.mark.gpu
