@@ -62,6 +62,7 @@ Partial8pFn partial8p_kernel(int mode) {
     case 9: return cosine_topk_partial8p_t<9>;
     case 12: return cosine_topk_partial8p_t<12>;
     case 15: return cosine_topk_partial8p_t<15>;
+    case 16: return cosine_topk_partial8p_t<16>;
   }
   TORCH_CHECK(false, "no 256x256 kernel for EPI_MODE ", mode);
 }
@@ -397,13 +398,16 @@ std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> emit_counts_probe(
 double probe8p(torch::Tensor queries, torch::Tensor corpus, int64_t mode,
                int64_t iters) {
   // Timing probe for 8p epilogue isolation (profiles/knn_kernel_history):
-  // mode 1 = no epilogue (GEMM core), 12 = hot sweep only (worst case:
-  // null thresholds make every ballot fire). Neither touches the emission
-  // buffers, so none are passed. Returns ms per launch.
+  // mode 1 = no epilogue (GEMM core, staggered wave groups), 16 = the same
+  // core on the lockstep schedule (A/B of the sync structure in one process
+  // on the same buffers), 12 = hot sweep only (worst case: null thresholds
+  // make every ballot fire). None touches the emission buffers, so none
+  // are passed. Returns ms per launch.
   check_bf16_2d(queries, "queries");
   check_bf16_2d(corpus, "corpus");
-  TORCH_CHECK(mode == 1 || mode == 12,
-              "probe8p mode must be 1 (GEMM core) or 12 (hot sweep), got ", mode);
+  TORCH_CHECK(mode == 1 || mode == 12 || mode == 16,
+              "probe8p mode must be 1 (GEMM core), 16 (lockstep GEMM core) or "
+              "12 (hot sweep), got ", mode);
   const KnnArgs a = knn_args(queries, corpus, (int)corpus.size(0));
   const Chunking ch = chunking(a.B, a.N, BM8, default_target(BM8));
   auto pscore = torch::empty({(long)a.B * ch.nchunks * KMAX}, a.f32());

@@ -500,13 +500,65 @@ __global__ __launch_bounds__(THREADS, 2) void cosine_topk_partial_t(
 // which is what frees the B image bytes early enough that the NEXT
 // window's staging can target the LIVE buffer:
 //
-//   staging schedule (per wave, reader-aligned 1 KiB pieces):
+//   staging schedule (per wave, reader-aligned 1 KiB pieces), LOCKSTEP
+//   modes (6, 16):
 //     window t, ph0: A(t+1) pieces 0,1      -> buf[(t+1)&1]  (unread now)
 //     window t, ph1: A(t+1) 2,3 + B(t+2) 0,1-> B into buf[t&1]: its B bytes
 //     window t, ph2: B(t+2) pieces 2,3         were consumed at ph0
-//   certification: one `s_waitcnt vmcnt(4)` at ph3 (before the barrier)
-//   leaves exactly B(t+2)'s 4 glds in flight and proves A(t+1) + B(t+1)
-//   (and older) landed -> the pipeline NEVER drains to vmcnt(0).
+//   STAGGERED modes (1, 9, 12, 15): the B issues sit one phase later,
+//     window t, ph0: A(t+1) 0,1   ph1: A(t+1) 2,3
+//     window t, ph2: B(t+2) 0,1   ph3: B(t+2) 2,3 (before the wait)
+//   certification (both): one `s_waitcnt vmcnt(4)` at ph3 (before the
+//   barrier) leaves exactly B(t+2)'s 4 glds in flight and proves A(t+1) +
+//   B(t+1) (and older) landed -> the pipeline NEVER drains to vmcnt(0)
+//   (except the chunk tail, where no B(t+2) exists: vmcnt(0) there).
+//
+// Each phase p of window t is: issue ds_reads + glds [+ ph3 wait];
+// barrier Ba(t,p); lgkmcnt(0); 16 MFMA; barrier Bb(t,p). So a phase's
+// ds_reads are ISSUED before its Ba and RETIRED before its Bb.
+//
+// Staggered wave groups (modes without a barrier/LDS epilogue). Waves w
+// and w+4 share a SIMD, i.e. group 0 (wr=0) and group 1 (wr=1) of the same
+// wc. Lockstep makes both read together and then compute together, and
+// the matrix pipe idles through every read+barrier segment. Group 1
+// therefore executes ONE extra s_barrier after the prologue and group 0
+// the matching one after the last tile's K loop: between any two
+// barriers one wave of each SIMD is in its MFMA segment while its partner
+// reads and stages. Barrier counts per wave are equal, so the final
+// "write partials" barrier lines up; the padded-chunk return precedes it.
+//
+// Ledger, in HARDWARE barrier indices n (counted from the first barrier
+// after the prologue's __syncthreads). Group 0: Ba(t,p) = 8t+2p,
+// Bb(t,p) = 8t+2p+1. Group 1: Ba(t,p) = 8t+2p+1, Bb(t,p) = 8t+2p+2.
+//   A-half(wr) [both buffers]: staged by group wr (wave wc stages quarter
+//     wc), read by group wr only (phase p reads quarter p). Group-private:
+//     all four waves see the same barrier indices, as in lockstep.
+//     WAR: A(t+1) overwrites A(t-1); its last reads (window t-1, ph3)
+//       retire before the group's Bb(t-1,3); the glds issue after it.
+//     RAW: the staging wave's ph3 vmcnt precedes Ba(t,3); group-mates
+//       issue their first A(t+1) read after Bb(t,3).
+//   B-half(h) rows (wc&1)*64..+64 [both buffers]: read at ph0 only, by
+//     waves (0,wc) and (1,wc); each stages the 32 rows wr*32..+32 of it.
+//     WAR, B(t+2) over B(t): group 0's reads of B(t) retire before n=8t+1,
+//       group 1's before n=8t+2. Earliest B(t+2) issue is ph2: group 0
+//       after n=8t+3, group 1 after n=8t+4 — both later than a barrier
+//       (8t+2) that every reader reached with its reads retired. (The
+//       lockstep ph1 slot is NOT safe here: group 0 would issue between
+//       8t+1 and 8t+2 while group 1 is still retiring those bytes.)
+//     RAW, B(t+1): group 0 certifies its rows before n=8t+6, group 1
+//       before n=8t+7 (each its own Ba(t,3)). Group 0 issues its B(t+1)
+//       reads after n=8t+7, group 1 after n=8t+8: each reader has passed
+//       a barrier the other group reached after its counted wait ("one
+//       barrier more" — exactly enough for group 0, one spare for group 1).
+//     vmcnt order at window t ph3: [B(t+1) 0-3 (window t-1 ph2,ph3)],
+//       A(t+1) 0-3, B(t+2) 0-3 -> vmcnt(4) leaves only B(t+2).
+//   Prologue: A(0), B(0), B(1) certified by vmcnt(0) + __syncthreads
+//     before either group's first read.
+//   lsc/lix lists: written before the first __syncthreads, read after the
+//     final barrier (modes 1, 15, 16); never touched in between.
+// Mode 6 keeps lockstep: its stash/drain epilogue shares LDS and barriers
+// across both groups. Mode 16 is mode 1 on the lockstep schedule, kept so
+// probe8p can A/B the two sync structures in one process.
 //
 // Reader-aligned staging makes per-wave vmcnt certification sound: a
 // wave stages exactly the quarter of each half-image that it (or its
@@ -578,6 +630,9 @@ __device__ __noinline__ void emit_stashed(
 //      scores >= the prepass floor go to a global candidate buffer
 //   12 = 9's hot sweep with the cold path compiled out (probe8p)
 //   15 = 9 with block-lifetime packed threshold vectors (=8pe2)
+//   16 = 1 on the lockstep schedule (probe8p A/B, tools/knn_probe.hip)
+// Modes 1, 9, 12, 15 run their two wave groups staggered by one barrier;
+// 6 and 16 run lockstep (ledger in the block comment above).
 // `stats` and `slab` are unused (they belonged to pruned modes) and stay
 // in the signature so kernel symbols and kernarg offsets do not move.
 template <int EPI_MODE>
@@ -591,6 +646,10 @@ __global__ __launch_bounds__(THREADS8, 2) void cosine_topk_partial8p_t(
     unsigned* __restrict__ ccount = nullptr, long ccap = 0,
     char* __restrict__ estash = nullptr) {
   constexpr bool EMIT = EPI_MODE == 9 || EPI_MODE == 12 || EPI_MODE == 15;
+  constexpr bool GEMM_ONLY = EPI_MODE == 1 || EPI_MODE == 16;
+  // staggered wave groups: only for the modes whose epilogue has no
+  // barrier and no LDS traffic (see the ledger above the kernel)
+  constexpr bool STAGGER = EPI_MODE == 1 || EMIT;
   __shared__ char smem[8 * HALF8 + 2 * BM8 * KMAX * 4 + 32];
   char* const smem0 = smem;
   // buffer b in {0,1}: A half h at b*4*HALF8 + h*HALF8; B half h at +2*HALF8
@@ -606,7 +665,9 @@ __global__ __launch_bounds__(THREADS8, 2) void cosine_topk_partial8p_t(
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
-  const int wid = tid >> 6;
+  // wave-uniform for the compiler: wr guards raw s_barriers below, which
+  // must sit behind a scalar branch
+  const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int g = lane >> 4;
   const int cl = lane & 15;
   const int wr = wid >> 2;  // row half
@@ -690,6 +751,11 @@ __global__ __launch_bounds__(THREADS8, 2) void cosine_topk_partial8p_t(
   for (int i = 0; i < 4; ++i) stage_b_piece(1, i);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
+  // stagger: group 1 (waves 4-7) runs one barrier behind group 0 from
+  // here to the end of the last tile's K loop
+  if constexpr (STAGGER) {
+    if (wr == 1) __builtin_amdgcn_s_barrier();
+  }
 
   const int total_windows = tiles_here * nkt;
 
@@ -742,7 +808,7 @@ __global__ __launch_bounds__(THREADS8, 2) void cosine_topk_partial8p_t(
     // per-lane threshold floors for this wave-half's two rows (rows
     // beyond B get +inf so clamped-row garbage never flags)
     float thr0 = NEG_INF, thr1 = NEG_INF;
-    if constexpr (EPI_MODE != 1) {
+    if constexpr (!GEMM_ONLY) {
       const int r0g = row0 + wr * 128 + lane;
       thr0 = (r0g < B) ? (rowthr ? dec_f32(rowthr[r0g]) : NEG_INF) : 1e38f;
       thr1 = (r0g + 64 < B) ? (rowthr ? dec_f32(rowthr[r0g + 64]) : NEG_INF)
@@ -777,7 +843,29 @@ __global__ __launch_bounds__(THREADS8, 2) void cosine_topk_partial8p_t(
               bf[n][kk] = read_frag(Bi, n * 16 + cl, kk * 4 + g);
         }
         // ---- staging issues (see schedule above)
-        if (qm == 0 && t + 1 < total_windows) {
+        if constexpr (STAGGER) {
+          if (qm == 0 && t + 1 < total_windows) {
+            stage_a_piece(t + 1, 0);
+            stage_a_piece(t + 1, 1);
+          } else if (qm == 1 && t + 1 < total_windows) {
+            stage_a_piece(t + 1, 2);
+            stage_a_piece(t + 1, 3);
+          } else if (qm == 2 && t + 2 < total_windows) {
+            stage_b_piece(t + 2, 0);
+            stage_b_piece(t + 2, 1);
+          } else if (qm == 3) {
+            // B(t+2) 2,3 go out BEFORE the counted wait, so the newest 4
+            // outstanding glds are still exactly B(t+2)'s: vmcnt(4)
+            // certifies A(t+1) and B(t+1). Chunk tail: no B(t+2), drain.
+            if (t + 2 < total_windows) {
+              stage_b_piece(t + 2, 2);
+              stage_b_piece(t + 2, 3);
+              asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+            } else {
+              asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            }
+          }
+        } else if (qm == 0 && t + 1 < total_windows) {
           stage_a_piece(t + 1, 0);
           stage_a_piece(t + 1, 1);
         } else if (qm == 1) {
@@ -816,9 +904,14 @@ __global__ __launch_bounds__(THREADS8, 2) void cosine_topk_partial8p_t(
         __builtin_amdgcn_s_barrier();  // read-retirement vs next glds
       }
     }
+    // group 0's make-up barrier pairs with group 1's last phase barrier;
+    // from here on every wave has executed the same number of barriers
+    if constexpr (STAGGER) {
+      if (wr == 0 && j == tiles_here - 1) __builtin_amdgcn_s_barrier();
+    }
 
     // ---- top-k epilogue ---------------------------------------------------
-    if constexpr (EPI_MODE == 1) {
+    if constexpr (GEMM_ONLY) {
 #pragma unroll
       for (int m = 0; m < 8; ++m)
 #pragma unroll

@@ -58,6 +58,7 @@ static const Entry kTable[] = {
     {"argmax128", cosine_topk_partial_t<4>, nullptr, false},
     {"fastbl8p", nullptr, cosine_topk_partial8p_t<6>, false},
     {"gemm8p", nullptr, cosine_topk_partial8p_t<1>, false},
+    {"gemm8plock", nullptr, cosine_topk_partial8p_t<16>, false},
 };
 constexpr int NE = sizeof(kTable) / sizeof(kTable[0]);
 
