@@ -93,6 +93,9 @@ class CanonicalFailureRecord(BaseModel):
 class FailureMatchRequest(BaseModel):
     signature_text: str
     failure_type: Optional[str] = None
+    # opt-in: apply failure_type inside the search (top-k OF that type)
+    # instead of after the global top-k cut, the reference's order
+    filter_first: bool = False
 
 
 class FailureMatch(BaseModel):

@@ -14,6 +14,11 @@ divergence from the reference: the reference scores every *version* row, so
 its top-5 can be five copies of one failure; this engine searches one row
 per identity and reports the latest version — strictly more informative,
 same wire shapes.
+
+Opt-in divergence: ``filter_first`` applies the ``failure_type`` of a match
+inside the search (each store row carries its type as an int32 label and
+the kernels skip other rows), so the answer is the top-k of that type
+instead of whatever of that type survived the global top-k cut.
 """
 
 from __future__ import annotations
@@ -21,7 +26,7 @@ from __future__ import annotations
 import json
 import threading
 from pathlib import Path
-from typing import Any, Dict, List, Optional, Tuple
+from typing import Any, Dict, List, Optional, Sequence, Tuple, Union
 
 import torch
 
@@ -54,6 +59,11 @@ class EmbeddingStore:
     Insertion appends rows at the live prefix; the search kernel only scans
     the first ``count`` rows (valid_n), so inserts while serving are safe
     under the engine lock.
+
+    Every row also carries an int32 label (-1 = unlabelled; 4 B beside a
+    1536-B bf16 row), one label tensor per segment, growing and splitting
+    with the rows. ``search(..., want=...)`` restricts each query to the
+    rows of one label inside the scan (``ops.cosine_topk_filtered``).
     """
 
     def __init__(
@@ -74,7 +84,11 @@ class EmbeddingStore:
         self._segments: List[torch.Tensor] = [
             torch.zeros(capacity, dim, dtype=self.dtype, device=self.device)
         ]
+        self._labels: List[torch.Tensor] = [self._new_labels(capacity)]
         self.count = 0
+
+    def _new_labels(self, n: int) -> torch.Tensor:
+        return torch.full((n,), -1, dtype=torch.int32, device=self.device)
 
     @property
     def capacity(self) -> int:
@@ -95,6 +109,9 @@ class EmbeddingStore:
                 fresh = torch.zeros(cap, self.dim, dtype=self.dtype, device=self.device)
                 fresh[: self.count] = self._segments[0][: self.count]
                 self._segments[0] = fresh
+                labels = self._new_labels(cap)
+                labels[: self.count] = self._labels[0][: self.count]
+                self._labels[0] = labels
             else:
                 # at scale: copy-free growth by a fixed segment quantum
                 self._segments.append(
@@ -102,29 +119,44 @@ class EmbeddingStore:
                         self.segment_rows, self.dim, dtype=self.dtype, device=self.device
                     )
                 )
+                self._labels.append(self._new_labels(self.segment_rows))
 
-    def adopt(self, data: torch.Tensor) -> None:
+    def adopt(self, data: torch.Tensor, labels: Optional[torch.Tensor] = None) -> None:
         """Take ownership of a pre-built [n, D] row tensor (zero copy) —
         used by benches/restore paths where the rows already live on the
-        device in the right dtype. Later appends grow segment-wise."""
+        device in the right dtype. Later appends grow segment-wise.
+        ``labels`` ([n] ints) default to all unlabelled."""
         assert data.dtype == self.dtype and data.shape[1] == self.dim
+        n = int(data.shape[0])
+        if labels is None:
+            lab = self._new_labels(n)
+        else:
+            assert labels.shape == (n,)
+            lab = labels.to(device=self.device, dtype=torch.int32).contiguous()
         self._segments = [data]
-        self.count = data.shape[0]
+        self._labels = [lab]
+        self.count = n
 
-    def append(self, rows: torch.Tensor) -> int:
+    def append(self, rows: torch.Tensor, labels: Optional[torch.Tensor] = None) -> int:
         """Append [n, D] rows (splitting across segments); returns the
-        first new row index."""
+        first new row index. ``labels`` ([n] ints) default to unlabelled."""
         n = rows.shape[0]
+        if labels is not None:
+            assert labels.shape == (n,)
+            labels = labels.to(device=self.device, dtype=torch.int32)
         self._grow_to(self.count + n)
         first = self.count
         written = 0
         base = 0
-        for seg in self._segments:
+        for seg, lab in zip(self._segments, self._labels):
             seg_rows = int(seg.shape[0])
             if self.count + written < base + seg_rows and written < n:
                 off = self.count + written - base
                 take = min(seg_rows - off, n - written)
                 seg[off : off + take] = rows[written : written + take].to(self.dtype)
+                # slots past the live prefix are -1 already (never reused)
+                if labels is not None:
+                    lab[off : off + take] = labels[written : written + take]
                 written += take
             base += seg_rows
         assert written == n
@@ -148,26 +180,57 @@ class EmbeddingStore:
         return out
 
     def search(
-        self, queries: torch.Tensor, k: int, valid_n: Optional[int] = None
+        self,
+        queries: torch.Tensor,
+        k: int,
+        valid_n: Optional[int] = None,
+        want: Optional[torch.Tensor] = None,
     ) -> Tuple[torch.Tensor, torch.Tensor]:
         """Top-k over the first ``valid_n`` rows (default: the live count).
         Passing a snapshot of ``count`` makes the search safe to run
         outside the engine lock while appends continue: rows below the
-        snapshot are immutable once written."""
+        snapshot are immutable once written.
+
+        ``want`` ([B] ints) restricts query b to the rows labelled
+        ``want[b]`` (negative: no restriction for that query); rows short
+        of k such rows are padded with (-inf, -1). ``want=None`` is the
+        unfiltered search."""
         q = queries.to(self.dtype)
         count = self.count if valid_n is None else min(int(valid_n), self.count)
         segs = self._live_segments(count)
+        w = None if want is None else want.to(device=self.device, dtype=torch.int32)
+
+        def topk(seg: torch.Tensor, labels: torch.Tensor, n: int):
+            if w is None:
+                return ops.cosine_topk(q, seg, k, valid_n=n)
+            return ops.cosine_topk_filtered(q, seg, labels, w, k, valid_n=n)
+
         if len(segs) <= 1:
-            return ops.cosine_topk(q, self._segments[0], k, valid_n=count)
+            return topk(self._segments[0], self._labels[0], count)
         parts_s, parts_i = [], []
-        for seg, valid, base in segs:
-            s, i = ops.cosine_topk(q, seg, k, valid_n=valid)
+        # the live segments are a prefix of _segments, so labels line up
+        for (seg, valid, base), labels in zip(segs, self._labels):
+            s, i = topk(seg, labels, valid)
             parts_i.append(torch.where(i < 0, i, i + base))
             parts_s.append(s)
         all_s = torch.cat(parts_s, dim=1)
         all_i = torch.cat(parts_i, dim=1)
         top_s, sel = torch.topk(all_s, min(k, all_s.shape[1]), dim=1)
         return top_s, all_i.gather(1, sel)
+
+    def label_range(self, start: int, end: int) -> torch.Tensor:
+        """Labels of rows [start, end) as one int32 tensor."""
+        end = min(end, self.count)
+        pieces = []
+        base = 0
+        for lab in self._labels:
+            lo, hi = max(start - base, 0), min(end - base, int(lab.shape[0]))
+            if lo < hi:
+                pieces.append(lab[lo:hi])
+            base += int(lab.shape[0])
+        if not pieces:
+            return self._labels[0][:0]
+        return pieces[0] if len(pieces) == 1 else torch.cat(pieces, dim=0)
 
     def row_range(self, start: int, end: int) -> torch.Tensor:
         """Rows [start, end) as one tensor (a view when they sit in a
@@ -299,20 +362,42 @@ class GfkbEngine:
         # store row -> identity
         self._row_identity: List[Tuple[str, str]] = []
         self._identity_row: Dict[Tuple[str, str], int] = {}
+        # failure_type -> store label id, in order of first appearance. Not
+        # persisted on its own: identities replay from the JSONL in the
+        # same order on restart, so the same ids come out again.
+        self._type_id: Dict[str, int] = {}
         self._rebuild_from_log()
 
     # -- bootstrap ---------------------------------------------------------
 
+    def _label_of(self, failure_type: str) -> int:
+        """Vocabulary id of a failure type, assigned on first sight."""
+        return self._type_id.setdefault(failure_type, len(self._type_id))
+
+    def _append_rows(self, rows: torch.Tensor, labels: torch.Tensor) -> int:
+        """Append to whatever store is attached. Distributed stores keep no
+        labels (filter-first is refused for them in match_batch)."""
+        if isinstance(self.store, EmbeddingStore):
+            return self.store.append(rows, labels)
+        return self.store.append(rows)
+
     def _restore_rows(self, identities: List[Tuple[str, str]]) -> None:
         """Install the embedding rows for ``identities`` (in order) into
         the current store: from the packed sidecar when it matches
-        (mmap + chunked H2D upload), else re-encode and rewrite it."""
+        (mmap + chunked H2D upload), else re-encode and rewrite it. The
+        sidecar holds embeddings only; the labels come from the identities
+        on either path."""
+        labels = torch.tensor(
+            [self._label_of(ft) for (ft, _sig) in identities], dtype=torch.int32
+        )
         if self.sidecar.count() == len(identities):
+            done = 0
             for chunk in self.sidecar.load_chunks():
-                self.store.append(chunk)
+                self._append_rows(chunk, labels[done : done + chunk.shape[0]])
+                done += chunk.shape[0]
         else:
             emb = self.encoder.encode_texts([sig for (_ft, sig) in identities])
-            self.store.append(emb)
+            self._append_rows(emb, labels)
             self.sidecar.rewrite(emb)
 
     def _rebuild_from_log(self) -> None:
@@ -374,7 +459,9 @@ class GfkbEngine:
                 self.failures.append(rec)
                 self._latest[key] = rec
                 emb = self.encoder.encode_texts([signature_text])
-                row = self.store.append(emb)
+                row = self._append_rows(
+                    emb, torch.tensor([self._label_of(failure_type)], dtype=torch.int32)
+                )
                 self.sidecar.append(emb)
                 self._row_identity.append(key)
                 self._identity_row[key] = row
@@ -396,12 +483,21 @@ class GfkbEngine:
             return rec, False
 
     def match(
-        self, signature_text: str, failure_type: Optional[str] = None, top_k: Optional[int] = None
+        self,
+        signature_text: str,
+        failure_type: Optional[str] = None,
+        top_k: Optional[int] = None,
+        filter_first: bool = False,
     ) -> List[FailureMatch]:
         """Top-k failures by cosine similarity, then optional type filter
-        (reference order: cut to top-k first, filter second)."""
+        (reference order: cut to top-k first, filter second). With
+        ``filter_first`` the type filter runs inside the search instead:
+        the top-k of the failures of that type."""
         return self.match_batch(
-            [signature_text], failure_types=[failure_type], top_k=top_k
+            [signature_text],
+            failure_types=[failure_type],
+            top_k=top_k,
+            filter_first=filter_first,
         )[0]
 
     def match_batch(
@@ -409,6 +505,7 @@ class GfkbEngine:
         signature_texts: List[str],
         failure_types: Optional[List[Optional[str]]] = None,
         top_k: Optional[int] = None,
+        filter_first: Union[bool, Sequence[bool]] = False,
     ) -> List[List[FailureMatch]]:
         """Match a whole batch of signatures with ONE fused-kernel launch.
 
@@ -418,21 +515,69 @@ class GfkbEngine:
         the GPU works. Rows below the snapshot are immutable, and their
         identity-map entries are written before ``count`` is bumped, so
         the lock-free mapping below is race-free.
+
+        ``filter_first`` (one bool, or one per query) opts a query that
+        names a ``failure_type`` into filter-first semantics: the search
+        itself is restricted to rows of that type, so the result is the
+        top-k OF that type rather than whatever of that type made the
+        global top-k. Queries without it keep the reference's post-filter
+        order; a batch may mix both, and a batch with none set takes the
+        unfiltered kernels. A type no failure has ever had matches nothing.
         """
         nq = len(signature_texts)
         k = top_k or self.top_k
+        first = (
+            [bool(filter_first)] * nq
+            if isinstance(filter_first, bool)
+            else [bool(f) for f in filter_first]
+        )
+        if len(first) != nq:
+            raise ValueError("filter_first must be one bool or one per query")
         with self._lock:
             store = self.store
             valid = store.count
+            # per query: want = the label id to search under (None: no
+            # filter in the search); unknown = filter-first on a type the
+            # vocabulary has never seen
+            want: List[Optional[int]] = [None] * nq
+            unknown = [False] * nq
+            for r in range(nq):
+                ft = failure_types[r] if failure_types else None
+                if first[r] and ft:
+                    if ft in self._type_id:
+                        want[r] = self._type_id[ft]
+                    else:
+                        unknown[r] = True
         if valid == 0:
             return [[] for _ in range(nq)]
-        q = self.encoder.encode_texts(signature_texts)
-        scores, idx = store.search(q, min(k, valid), valid_n=valid)
+        filtered = any(w is not None for w in want)
+        if (filtered or any(unknown)) and not isinstance(store, EmbeddingStore):
+            raise NotImplementedError(
+                f"filter_first is not supported on {type(store).__name__}: "
+                "sharded and distributed stores keep no row labels, and "
+                "post-filtering instead would silently change the result"
+            )
+        # unknown types cannot match: search only the other queries
+        live = [r for r in range(nq) if not unknown[r]]
+        if not live:
+            return [[] for _ in range(nq)]
+        q = self.encoder.encode_texts([signature_texts[r] for r in live])
+        if filtered:
+            want_t = torch.tensor(
+                [-1 if want[r] is None else want[r] for r in live], dtype=torch.int32
+            )
+            scores, idx = store.search(q, min(k, valid), valid_n=valid, want=want_t)
+        else:
+            scores, idx = store.search(q, min(k, valid), valid_n=valid)
+        slot = {r: j for j, r in enumerate(live)}
         results: List[List[FailureMatch]] = []
         for r in range(nq):
             failure_type = failure_types[r] if failure_types else None
             out: List[FailureMatch] = []
-            for s, i in zip(scores[r].tolist(), idx[r].tolist()):
+            if unknown[r]:
+                results.append(out)
+                continue
+            for s, i in zip(scores[slot[r]].tolist(), idx[slot[r]].tolist()):
                 if i < 0 or i >= len(self._row_identity):
                     # rows the engine has no identity for (e.g. a pre-loaded
                     # corpus adopted under the engine) can win the similarity

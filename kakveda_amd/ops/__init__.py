@@ -6,6 +6,9 @@ Kernels (kakveda_amd/ops/hip/):
   Replaces the reference's per-request TF-IDF refit + full-corpus cosine
   (/root/reference/services/shared/similarity.py:14-20,
   /root/reference/services/gfkb/app.py:79-102).
+- cosine_topk_filtered — the same search with a per-query label predicate
+  pushed into the scan (filtered instantiations of the 128x128 list kernel
+  and of the streaming small-batch kernel; exact at any selectivity).
 - l2normalize_ — in-place row L2-normalisation (bf16, vectorised loads).
 - embedding_bag — weighted gather-sum over the hashed-feature table
   (the trace-encoder front end).
@@ -111,6 +114,86 @@ def cosine_topk_ref(
     if kk < k:
         pad_s = torch.full((queries.shape[0], k - kk), float("-inf"), device=queries.device)
         pad_i = torch.full((queries.shape[0], k - kk), -1, dtype=idx.dtype, device=queries.device)
+        scores = torch.cat([scores, pad_s], dim=1)
+        idx = torch.cat([idx, pad_i], dim=1)
+    return scores.float(), idx.long()
+
+
+def cosine_topk_filtered(
+    queries: torch.Tensor,
+    corpus: torch.Tensor,
+    labels: torch.Tensor,
+    want: torch.Tensor,
+    k: int,
+    valid_n: Optional[int] = None,
+) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``cosine_topk`` with a per-query label predicate pushed into the scan.
+
+    labels: int32 [N], one per corpus row (-1 = unlabelled); want: int32 [B],
+    one per query. Corpus row j is eligible for query b iff
+    ``want[b] < 0 or labels[j] == want[b]``, so a batch may mix filtered and
+    unfiltered queries. Returns (scores f32 [B, k], idx i64 [B, k]) sorted
+    descending; a query with fewer than k eligible rows is padded with
+    (-inf, -1), as is everything past KMAX columns on GPU.
+
+    The search is exact whatever the selectivity: the kernels mask
+    ineligible rows before any pruning threshold is formed (see
+    ops/hip/kernels_impl.h), they do not over-fetch and post-filter.
+    """
+    n = int(valid_n) if valid_n is not None else corpus.shape[0]
+    B = queries.shape[0]
+    if n <= 0:
+        return (
+            torch.full((B, k), float("-inf"), dtype=torch.float32, device=queries.device),
+            torch.full((B, k), -1, dtype=torch.int64, device=queries.device),
+        )
+    if queries.device.type != "cuda":
+        return cosine_topk_filtered_ref(queries, corpus, labels, want, k, n)
+    ext = _require_ext()
+    kk = min(int(k), KMAX)
+    scores, idx = ext.cosine_topk_filtered(
+        queries,
+        corpus,
+        labels.to(device=corpus.device, dtype=torch.int32).contiguous(),
+        want.to(device=queries.device, dtype=torch.int32).contiguous(),
+        kk,
+        n,
+    )
+    # empty slots leave the kernels as (-1e30 or -inf, -1): one sentinel out
+    scores = torch.where(idx < 0, torch.full_like(scores, float("-inf")), scores)
+    if kk < k:
+        pad_s = torch.full((B, k - kk), float("-inf"), dtype=scores.dtype, device=scores.device)
+        pad_i = torch.full((B, k - kk), -1, dtype=idx.dtype, device=idx.device)
+        scores = torch.cat([scores, pad_s], dim=1)
+        idx = torch.cat([idx, pad_i], dim=1)
+    return scores, idx
+
+
+def cosine_topk_filtered_ref(
+    queries: torch.Tensor,
+    corpus: torch.Tensor,
+    labels: torch.Tensor,
+    want: torch.Tensor,
+    k: int,
+    valid_n: Optional[int] = None,
+) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Plain-PyTorch reference of ``cosine_topk_filtered`` (fp32 accumulate):
+    ineligible columns are scored -inf, and whatever of them reaches the
+    top-k of a sparsely populated label is reported as a pad, never as an
+    index of a masked row."""
+    n = int(valid_n) if valid_n is not None else corpus.shape[0]
+    B = queries.shape[0]
+    kk = min(k, n)
+    sims = queries.float() @ corpus[:n].float().t()
+    lab = labels[:n].to(sims.device).long()
+    w = want.to(sims.device).long()
+    eligible = (w[:, None] < 0) | (lab[None, :] == w[:, None])
+    sims = sims.masked_fill(~eligible, float("-inf"))
+    scores, idx = torch.topk(sims, kk, dim=1)
+    idx = torch.where(torch.isinf(scores) & (scores < 0), torch.full_like(idx, -1), idx)
+    if kk < k:
+        pad_s = torch.full((B, k - kk), float("-inf"), device=queries.device)
+        pad_i = torch.full((B, k - kk), -1, dtype=idx.dtype, device=queries.device)
         scores = torch.cat([scores, pad_s], dim=1)
         idx = torch.cat([idx, pad_i], dim=1)
     return scores.float(), idx.long()

@@ -47,11 +47,24 @@ Partial128Fn partial128_kernel(int mode) {
   TORCH_CHECK(false, "no 128x128 kernel for EPI_MODE ", mode);
 }
 
+// The label filter of a cosine_topk_filtered request (null/null: none).
+// Every launch of one request gets the same Filter: thresholds published
+// under one eligibility rule must not prune under another (kernels_impl.h).
+struct Filter {
+  const int* labels = nullptr;  // i32 [N]
+  const int* want = nullptr;    // i32 [B]
+  explicit operator bool() const { return labels != nullptr; }
+};
+
 void launch_partial128(int mode, dim3 grid, const KnnArgs& a, float* pscore,
-                       int* pidx, int chunk_tiles, int stride, unsigned* rowthr) {
-  hipLaunchKernelGGL(partial128_kernel(mode), grid, dim3(THREADS), 0, a.stream,
-                     a.q, a.c, pscore, pidx, a.B, a.N, a.D, chunk_tiles, stride,
-                     rowthr, (unsigned long long*)nullptr);
+                       int* pidx, int chunk_tiles, int stride, unsigned* rowthr,
+                       Filter f = {}) {
+  TORCH_CHECK(!f || mode == 11, "the filtered 128x128 kernel is EPI_MODE 11 only");
+  const Partial128Fn filtered = cosine_topk_partial_t<11, true>;
+  hipLaunchKernelGGL(f ? filtered : partial128_kernel(mode), grid,
+                     dim3(THREADS), 0, a.stream, a.q, a.c, pscore, pidx,
+                     a.B, a.N, a.D, chunk_tiles, stride, rowthr,
+                     (unsigned long long*)nullptr, f.labels, f.want);
 }
 
 using Partial8pFn = decltype(&cosine_topk_partial8p_t<9>);
@@ -95,7 +108,8 @@ struct Floors {
   torch::Tensor rowthr, samp_s, samp_i;
 };
 
-Floors run_emission_floors(const KnnArgs& a, int preg, int prepass_mode) {
+Floors run_emission_floors(const KnnArgs& a, int preg, int prepass_mode,
+                           Filter flt = {}) {
   Floors f{new_rowthr(a), torch::empty({(long)a.B, (long)KMAX}, a.f32()),
            torch::empty({(long)a.B, (long)KMAX}, a.i64())};
   auto ppre_s = torch::empty({(long)a.B * preg * KMAX}, a.f32());
@@ -104,7 +118,11 @@ Floors run_emission_floors(const KnnArgs& a, int preg, int prepass_mode) {
   // 256-row-tile 8p main launch
   launch_partial128(prepass_mode, dim3(preg, (a.B + BM - 1) / BM), a,
                     ppre_s.data_ptr<float>(), ppre_i.data_ptr<int>(), PRE_TILES,
-                    preg, (unsigned*)f.rowthr.data_ptr<int>());
+                    preg, (unsigned*)f.rowthr.data_ptr<int>(), flt);
+  // (filtered: the sample lists hold eligible columns only, so the floor
+  // published below is the 8th best ELIGIBLE sampled score; with fewer than
+  // 8 eligible samples nothing is published and the main launch emits
+  // every eligible row)
   // block-per-row merge: the thread-per-row variant serial-scanned 2k
   // entries per thread (0.9 ms/step at preg=256)
   hipLaunchKernelGGL(topk_merge, dim3(a.B), dim3(THREADS), 0, a.stream,
@@ -142,10 +160,10 @@ void launch_emit8p(int mode, const KnnArgs& a, const Chunking& ch,
 
 std::tuple<torch::Tensor, torch::Tensor> cosine_topk_impl(
     const torch::Tensor& queries, const torch::Tensor& corpus, int k, int N,
-    const KnnEnv& env, bool allow_emission) {
+    const KnnEnv& env, bool allow_emission, Filter flt = {}) {
   const KnnArgs a = knn_args(queries, corpus, N);
   const int B = a.B;
-  const KnnPlan p = plan_cosine_topk(B, N, k, env, allow_emission);
+  const KnnPlan p = plan_cosine_topk(B, N, k, env, allow_emission, (bool)flt);
   const Chunking& ch = p.ch;
 
   auto pscore = torch::empty({(long)B * ch.nchunks * KMAX}, a.f32());
@@ -157,20 +175,36 @@ std::tuple<torch::Tensor, torch::Tensor> cosine_topk_impl(
   if (p.merge == MergeKernel::Emit) {
     // candidates go to a per-row global buffer sized for ~8N/sample
     // expected emissions with ~25x headroom
-    const Floors f = p.prepass ? run_emission_floors(a, p.preg, p.prepass_mode)
-                               : Floors{new_rowthr(a), {}, {}};
+    const Floors f = p.prepass
+                         ? run_emission_floors(a, p.preg, p.prepass_mode, flt)
+                         : Floors{new_rowthr(a), {}, {}};
     EmitBufs e = new_emit_bufs(a, p.cap, ch);
-    if (p.main == MainKernel::SmallB) {
+    if (p.main == MainKernel::SmallB && flt) {
+      hipLaunchKernelGGL(smallb_emit_kernel_v4<true>, dim3(p.smallb_blocks),
+                         dim3(256), (size_t)B * a.D * 2, a.stream, a.q, a.c, B,
+                         (long)N, a.D, (const unsigned*)f.rowthr.data_ptr<int>(),
+                         (unsigned long long*)e.cand.data_ptr<int64_t>(),
+                         (unsigned*)e.ccount.data_ptr<int>(), p.cap, flt.labels,
+                         flt.want);
+    } else if (p.main == MainKernel::SmallB) {
       // Default: the v4 8-lanes-per-row remap (same-box A/B at 10M:
       // +1.5% at B=1, +13.6% at B=4, exact parity — see
       // profiles/knn_kernel_history.md). KAKVEDA_SMALLB=2 reverts to the
       // per-lane-row streaming kernel (v2).
-      hipLaunchKernelGGL(p.mode == 2 ? smallb_emit_kernel : smallb_emit_kernel_v4,
-                         dim3(p.smallb_blocks), dim3(256), (size_t)B * a.D * 2,
-                         a.stream, a.q, a.c, B, (long)N, a.D,
-                         (const unsigned*)f.rowthr.data_ptr<int>(),
-                         (unsigned long long*)e.cand.data_ptr<int64_t>(),
-                         (unsigned*)e.ccount.data_ptr<int>(), p.cap);
+      if (p.mode == 2)
+        hipLaunchKernelGGL(smallb_emit_kernel, dim3(p.smallb_blocks), dim3(256),
+                           (size_t)B * a.D * 2, a.stream, a.q, a.c, B, (long)N,
+                           a.D, (const unsigned*)f.rowthr.data_ptr<int>(),
+                           (unsigned long long*)e.cand.data_ptr<int64_t>(),
+                           (unsigned*)e.ccount.data_ptr<int>(), p.cap);
+      else
+        hipLaunchKernelGGL(smallb_emit_kernel_v4<false>, dim3(p.smallb_blocks),
+                           dim3(256), (size_t)B * a.D * 2, a.stream, a.q, a.c,
+                           B, (long)N, a.D,
+                           (const unsigned*)f.rowthr.data_ptr<int>(),
+                           (unsigned long long*)e.cand.data_ptr<int64_t>(),
+                           (unsigned*)e.ccount.data_ptr<int>(), p.cap,
+                           (const int*)nullptr, (const int*)nullptr);
     } else {
       launch_emit8p(p.mode, a, ch, pscore, pidx, f.rowthr, e, p.cap);
     }
@@ -196,7 +230,7 @@ std::tuple<torch::Tensor, torch::Tensor> cosine_topk_impl(
                 "falling back to the list-epilogue kernel for this batch\n",
                 mx, p.cap);
       }
-      return cosine_topk_impl(queries, corpus, k, N, env, false);
+      return cosine_topk_impl(queries, corpus, k, N, env, false, flt);
     }
     return {out_score, out_idx};
   }
@@ -213,7 +247,7 @@ std::tuple<torch::Tensor, torch::Tensor> cosine_topk_impl(
   if (p.prepass)
     launch_partial128(p.prepass_mode, dim3(p.preg, (B + BM - 1) / BM), a,
                       pscore.data_ptr<float>(), pidx.data_ptr<int>(), PRE_TILES,
-                      ch.nchunks, thr);
+                      ch.nchunks, thr, flt);
   if (p.main == MainKernel::Stash8p)
     launch_partial8p(p.mode, grid, a, pscore.data_ptr<float>(),
                      pidx.data_ptr<int>(), ch.chunk_tiles, ch.nchunks, thr,
@@ -221,7 +255,7 @@ std::tuple<torch::Tensor, torch::Tensor> cosine_topk_impl(
   else  // List128, or Argmax128 (k=1: per-row max, no thresholds)
     launch_partial128(p.mode, grid, a, pscore.data_ptr<float>(),
                       pidx.data_ptr<int>(), ch.chunk_tiles, ch.nchunks,
-                      p.main == MainKernel::Argmax128 ? nullptr : thr);
+                      p.main == MainKernel::Argmax128 ? nullptr : thr, flt);
   if (p.merge == MergeKernel::Small)
     hipLaunchKernelGGL(topk_merge_small, dim3((B + 255) / 256), dim3(256), 0,
                        a.stream, pscore.data_ptr<float>(), pidx.data_ptr<int>(),
@@ -252,6 +286,36 @@ std::tuple<torch::Tensor, torch::Tensor> cosine_topk(
   // anything is launched (knn_plan.h).
   static const KnnEnv env = parse_knn_env(std::getenv);
   return cosine_topk_impl(queries, corpus, (int)k, N, env, true);
+}
+
+std::tuple<torch::Tensor, torch::Tensor> cosine_topk_filtered(
+    torch::Tensor queries, torch::Tensor corpus, torch::Tensor labels,
+    torch::Tensor want, int64_t k, int64_t valid_n) {
+  // cosine_topk restricted, per query row b, to the corpus rows j with
+  // want[b] < 0 || labels[j] == want[b]. Rows short of k eligible corpus
+  // rows come back padded with the kernels' (-1e30 or -inf, -1) sentinels,
+  // which the Python op normalises.
+  check_bf16_2d(queries, "queries");
+  check_bf16_2d(corpus, "corpus");
+  const int D = queries.size(1);
+  const int N = (int)valid_n;
+  TORCH_CHECK(corpus.size(1) == D, "dim mismatch");
+  TORCH_CHECK(N >= 1 && N <= corpus.size(0), "valid_n out of range");
+  TORCH_CHECK(D % BK == 0, "D must be a multiple of ", BK);
+  TORCH_CHECK(k >= 1 && k <= KMAX, "k must be in [1,", KMAX, "]");
+  TORCH_CHECK(labels.is_cuda() && labels.device() == corpus.device() &&
+                  labels.scalar_type() == torch::kInt32 && labels.dim() == 1 &&
+                  labels.is_contiguous() && labels.size(0) >= N,
+              "labels must be contiguous 1-D i32 on the corpus device with at "
+              "least valid_n entries");
+  TORCH_CHECK(want.is_cuda() && want.device() == queries.device() &&
+                  want.scalar_type() == torch::kInt32 && want.dim() == 1 &&
+                  want.is_contiguous() && want.size(0) == queries.size(0),
+              "want must be contiguous 1-D i32 on the query device with one "
+              "entry per query row");
+  static const KnnEnv env = parse_knn_env(std::getenv);
+  return cosine_topk_impl(queries, corpus, (int)k, N, env, true,
+                          Filter{labels.data_ptr<int>(), want.data_ptr<int>()});
 }
 
 void l2normalize_(torch::Tensor t, int64_t start_row, int64_t end_row) {
@@ -435,6 +499,8 @@ double probe8p(torch::Tensor queries, torch::Tensor corpus, int64_t mode,
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("cosine_topk", &cosine_topk, "fused cosine top-k (MFMA + LDS top-k)");
+  m.def("cosine_topk_filtered", &cosine_topk_filtered,
+        "cosine top-k over the corpus rows whose label matches each query's");
   m.def("l2normalize_", &l2normalize_, "in-place row L2 normalisation");
   m.def("embedding_bag", &embedding_bag, "weighted embedding bag");
   m.def("kmeans_update", &kmeans_update, "segmented centroid sum + counts");

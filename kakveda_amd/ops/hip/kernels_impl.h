@@ -161,13 +161,29 @@ __device__ __noinline__ void topk_extract_group(
 //      shfl_xor max reduce — the PRODUCTION DEFAULT (754 TF vs 642 for
 //      mode 0 at B=4096 x N=2M)
 // `stats` is unused (it belonged to a pruned counting mode) and stays in
-// the signature so kernel symbols and kernarg offsets do not move.
-template <int EPI_MODE>
+// the signature so kernarg offsets do not move.
+//
+// FILTER (mode 11 only) is the label-filtered search: corpus column j is
+// eligible for query row b iff want[b] < 0 || labels[j] == want[b]
+// (labels i32 [N], want i32 [B]). An ineligible column's score becomes
+// NEG_INF exactly where out-of-range columns (col >= N) already do, ahead
+// of the ballot pre-check, so the lists only ever hold eligible columns
+// and everything downstream (insert, rowthr publish, partial write) is
+// unchanged: a full list's minimum is a lower bound of that row's k-th
+// best ELIGIBLE score. INVARIANT: every launch that reads or publishes
+// rowthr on behalf of a filtered request applies the same (labels, want);
+// a threshold published by an unfiltered launch would prune eligible rows.
+// labels/want trail the existing arguments (offsets unchanged) and are
+// never read by the FILTER=false instantiations.
+template <int EPI_MODE, bool FILTER = false>
 __global__ __launch_bounds__(THREADS, 2) void cosine_topk_partial_t(
     const bf16_t* __restrict__ Q, const bf16_t* __restrict__ C,
     float* __restrict__ partial_score, int* __restrict__ partial_idx,
     int B, int N, int D, int chunk_tiles, int nchunks,
-    unsigned* rowthr = nullptr, unsigned long long* stats = nullptr) {
+    unsigned* rowthr = nullptr, unsigned long long* stats = nullptr,
+    const int* __restrict__ labels = nullptr,
+    const int* __restrict__ want = nullptr) {
+  static_assert(!FILTER || EPI_MODE == 11, "only mode 11 has a filtered form");
   constexpr bool REG_THR = EPI_MODE == 8 || EPI_MODE == 9 || EPI_MODE == 11;
   constexpr bool INLINE_INSERT = EPI_MODE == 9 || EPI_MODE == 11;
   constexpr bool BALLOT_CHECK = EPI_MODE == 11;
@@ -244,6 +260,15 @@ __global__ __launch_bounds__(THREADS, 2) void cosine_topk_partial_t(
   float rmin_reg = NEG_INF;
   (void)rmin_reg;
 
+  // FILTER: lane l of each wave caches want[] for row wr*64+l for the
+  // block's lifetime (-1 = unfiltered, also for the padding rows >= B); the
+  // (m, reg) loop broadcasts it with one shfl, as it does rmin_reg.
+  int want_reg = -1;
+  (void)want_reg;
+  if constexpr (FILTER) {
+    if (row0 + wr * 64 + lane < B) want_reg = want[row0 + wr * 64 + lane];
+  }
+
   for (int j = 0; j < tiles_here; ++j) {
     const int col0 = (tile0 + j) * BN;
 
@@ -313,6 +338,18 @@ __global__ __launch_bounds__(THREADS, 2) void cosine_topk_partial_t(
           asm volatile("" ::"v"(acc[m][n]));
     } else {
       const int colb = col0 + wc * 64 + cl;
+      // FILTER: this lane's 4 column labels, loaded once per column tile.
+      // (Folding them with the group's 16 wants into two registers of
+      // eligibility bits ahead of the loop was tried: 38 spilled VGPRs
+      // against 2 for this form; the kernel sits at the 256-VGPR limit.)
+      int lab0 = -1, lab1 = -1, lab2 = -1, lab3 = -1;
+      (void)lab0; (void)lab1; (void)lab2; (void)lab3;
+      if constexpr (FILTER) {
+        if (colb + 0 < N) lab0 = labels[colb + 0];
+        if (colb + 16 < N) lab1 = labels[colb + 16];
+        if (colb + 32 < N) lab2 = labels[colb + 32];
+        if (colb + 48 < N) lab3 = labels[colb + 48];
+      }
 #pragma unroll
       for (int m = 0; m < 4; ++m) {
 #pragma unroll
@@ -335,6 +372,15 @@ __global__ __launch_bounds__(THREADS, 2) void cosine_topk_partial_t(
           float w1 = (colb + 16 < N) ? acc[m][1][reg] : NEG_INF;
           float w2 = (colb + 32 < N) ? acc[m][2][reg] : NEG_INF;
           float w3 = (colb + 48 < N) ? acc[m][3][reg] : NEG_INF;
+          if constexpr (FILTER) {
+            const int wt = __shfl(want_reg, m * 16 + g * 4 + reg, 64);
+            if (wt >= 0) {
+              if (lab0 != wt) w0 = NEG_INF;
+              if (lab1 != wt) w1 = NEG_INF;
+              if (lab2 != wt) w2 = NEG_INF;
+              if (lab3 != wt) w3 = NEG_INF;
+            }
+          }
           // BALLOT_CHECK: one ballot replaces the 4-deep shfl_xor max
           // reduce in the pre-check (same predicate: does ANY lane of
           // the group beat the threshold) — halves the cross-lane
@@ -1287,16 +1333,44 @@ __global__ __launch_bounds__(256) void smallb_emit_kernel(
 // waves/SIMD occupancy, NOT cache behaviour. Exactness: identical
 // emission contract to v2 — every score >= the shared prepass floor is
 // emitted; tail rows are clamped for the load and guarded at emission.
+//
+// FILTER is the label-filtered form (eligibility rule: see
+// cosine_topk_partial_t): want[0..B) sits in LDS beside fl, each row
+// group's ch == 0 lane loads its row's label, and a score is emitted only
+// when it clears the floor AND its row is eligible for that query. The
+// floors it reads must come from a prepass run with the same (labels,
+// want). labels/want trail the existing arguments and are never read by
+// the FILTER=false instantiation. (A shared __forceinline__ body under two
+// plain kernels was tried first: the unfiltered kernel no longer compiled
+// to the instructions it had.)
+template <bool FILTER = false>
 __global__ __launch_bounds__(256) void smallb_emit_kernel_v4(
     const bf16_t* __restrict__ Q, const bf16_t* __restrict__ C, int B,
     long N, int D, const unsigned* __restrict__ rowthr,
     unsigned long long* __restrict__ cand, unsigned* __restrict__ ccount,
-    long ccap) {
+    long ccap, const int* __restrict__ labels = nullptr,
+    const int* __restrict__ want = nullptr) {
   extern __shared__ char qmem[];  // [B][D] bf16 queries
   __shared__ float fl[8];
+  const int* wl = nullptr;
+  (void)wl;
   for (int i = threadIdx.x; i < B * (D / 8); i += 256)
     ((bf16x8*)qmem)[i] = ((const bf16x8*)Q)[i];
   if (threadIdx.x < B) fl[threadIdx.x] = dec_f32(rowthr[threadIdx.x]);
+  if constexpr (FILTER) {
+    __shared__ int wls[8];  // no LDS in the unfiltered kernel
+    if (threadIdx.x < B) wls[threadIdx.x] = want[threadIdx.x];
+    wl = wls;
+    // The floor was scored by the MFMA prepass, the rows below by VALU
+    // sums in another order. Both add the same exact bf16 products in
+    // fp32, each within (D-1) * 2^-24 * sum|q_i c_i| (<= (D-1) * 2^-24 for
+    // unit rows) of the true value, so they differ by < D * 2^-23. When a
+    // sampled row IS a query's k-th best (a sparse label, or a sample that
+    // covers the whole corpus) that difference can put its streamed score
+    // under its own floor; lower the floor by twice the bound. NEG_INF
+    // (no floor published) absorbs the subtraction.
+    if (threadIdx.x < B) fl[threadIdx.x] -= (float)D * 0x1p-22f;
+  }
   __syncthreads();
 
   const int lane = threadIdx.x & 63;
@@ -1308,6 +1382,11 @@ __global__ __launch_bounds__(256) void smallb_emit_kernel_v4(
        r0 += (long)gridDim.x * 32) {
     const long r = r0 + rr < N ? r0 + rr : N - 1;  // clamp tail loads
     const bf16x8* row = (const bf16x8*)(C + r * D);
+    int lab = -1;
+    (void)lab;
+    if constexpr (FILTER) {
+      if (ch == 0 && r0 + rr < N) lab = labels[r0 + rr];
+    }
     f32x4 accv[8];
 #pragma unroll
     for (int b = 0; b < 8; ++b) accv[b] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -1350,7 +1429,9 @@ __global__ __launch_bounds__(256) void smallb_emit_kernel_v4(
         s += __shfl_xor(s, 1, 64);
         s += __shfl_xor(s, 2, 64);
         s += __shfl_xor(s, 4, 64);  // the row group's 8 lanes now agree
-        if (ch == 0 && r0 + rr < N && s >= fl[b]) {
+        bool eligible = true;
+        if constexpr (FILTER) eligible = wl[b] < 0 || lab == wl[b];
+        if (ch == 0 && r0 + rr < N && s >= fl[b] && eligible) {
           const unsigned pos = atomicAdd(&ccount[b], 1u);
           if (pos < (unsigned)ccap)
             cand[(size_t)b * ccap + pos] =

@@ -17,6 +17,10 @@ constexpr int BM8 = 256;  // 256x256 8-phase kernels
 constexpr int BN8 = 256;
 constexpr int KMAX = 8;       // top-k list capacity per row
 constexpr int PRE_TILES = 8;  // column tiles each prepass block samples
+// prepass grid.x (sampled chunks): threshold warming, and the 4x wider
+// sample behind the emission floors
+constexpr int PREG_WARM = 64;
+constexpr int PREG_EMIT = 256;
 
 // Selection thresholds (corpus columns / query rows).
 constexpr int MIN_N_8P = 4096;     // 256x256 tiles need a corpus this big
@@ -110,10 +114,44 @@ struct KnnPlan {
   MergeKernel merge;
 };
 
+// Label-filtered search (cosine_topk_filtered). Only two kernels carry the
+// filter: the streaming small-batch kernel (v4) and the 128x128 mode-11
+// list kernel, which also runs every prepass. So the filtered table is
+//   emission allowed, N >= MIN_N_EMIT, B <= SMALLB_MAX -> SmallB (4) + floors
+//   everything else, k == 1 included                   -> List128 (11)
+// on 128-row tiles throughout. KAKVEDA_KNN_KERNEL and KAKVEDA_SMALLB select
+// nothing here (no other kernel applies the filter; parsing still rejects
+// bad values); the geometry knobs (TARGET, PREG, PREPASS, EMIT_CAP) act as
+// on the unfiltered path. The 8p core has no filtered epilogue.
+inline KnnPlan plan_cosine_topk_filtered(int B, int N, int k, const KnnEnv& env,
+                                         bool allow_emission) {
+  KnnPlan p;
+  const bool emit = allow_emission && N >= MIN_N_EMIT && B <= SMALLB_MAX;
+  p.tile = BM;
+  p.ch = chunking(B, N, BM, env.target > 0 ? env.target : default_target(BM));
+  p.preg = std::min(env.preg > 0 ? env.preg : (emit ? PREG_EMIT : PREG_WARM), p.ch.nchunks) & ~7;
+  p.prepass_mode = 11;
+  const bool psmall = p.ch.ntiles <= p.preg * PRE_TILES * 32;
+  p.prepass = (emit || (k > 1 && p.ch.ntiles >= p.preg * PRE_TILES &&
+                        (env.prepass >= 0 ? env.prepass == 1 : psmall))) &&
+              p.preg >= 8;
+  p.prepass_compact = emit && p.prepass;
+  p.cap = env.cap;
+  p.smallb_blocks = (int)std::min((long)((N + 255) / 256), 8192L);
+  p.main = emit ? MainKernel::SmallB : MainKernel::List128;
+  p.mode = emit ? 4 : 11;
+  p.merge = emit                          ? MergeKernel::Emit
+            : p.ch.nchunks * KMAX <= 1024 ? MergeKernel::Small
+                                          : MergeKernel::Merge;
+  return p;
+}
+
 // allow_emission=false is the overflow fallback: the same request replanned
-// without the emission path.
+// without the emission path. filtered=true plans a label-filtered request
+// (above); filtered=false is the unfiltered table, unchanged.
 inline KnnPlan plan_cosine_topk(int B, int N, int k, const KnnEnv& env,
-                                bool allow_emission) {
+                                bool allow_emission, bool filtered = false) {
+  if (filtered) return plan_cosine_topk_filtered(B, N, k, env, allow_emission);
   KnnPlan p;
   // Emission (8p GEMM core + threshold-emission epilogue + emit_merge_topk)
   // needs the prepass floors, so only for corpora big enough to carry one.
@@ -140,7 +178,7 @@ inline KnnPlan plan_cosine_topk(int B, int N, int k, const KnnEnv& env,
   // emission floors tighten with sample size (E[emitted/row] ~ 8N/sample):
   // a 4x bigger prepass for the emission path. grid.x must stay <= nchunks
   // so every prepass block's partial slot [row][chunk_id] is in bounds.
-  p.preg = std::min(env.preg > 0 ? env.preg : (emit ? 256 : 64), p.ch.nchunks) & ~7;
+  p.preg = std::min(env.preg > 0 ? env.preg : (emit ? PREG_EMIT : PREG_WARM), p.ch.nchunks) & ~7;
   // Pay the prepass only when the sample is a meaningful fraction of the
   // corpus (>= ~3%): below that its published floor is weaker than what
   // the main launch's own publishes converge to almost immediately

@@ -11,7 +11,7 @@ latency-bound; compute-heavy local search dominates.
 
 from __future__ import annotations
 
-from typing import Tuple
+from typing import Optional, Tuple
 
 import torch
 import torch.distributed as td
@@ -75,12 +75,22 @@ class ShardedStore:
         out = local_idx * self.world + self.rank
         return torch.where(local_idx < 0, local_idx, out)
 
-    def search(self, queries: torch.Tensor, k: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    def search(
+        self, queries: torch.Tensor, k: int, want: Optional[torch.Tensor] = None
+    ) -> Tuple[torch.Tensor, torch.Tensor]:
         """Global top-k: local fused search + all-gather + merge.
 
         Returns (scores f32 [B, k], global ids i64 [B, k]) identical on all
         ranks, equal to a single-store search over the same data.
+
+        Label-filtered search (``want``) is a single-store feature so far:
+        shards carry no row labels, so asking for it raises.
         """
+        if want is not None:
+            raise NotImplementedError(
+                "ShardedStore has no label-filtered search (shards keep no "
+                "row labels); filter-first matching needs a single-store engine"
+            )
         B = queries.shape[0]
         scores, lidx = self.local.search(queries, k)
         gidx = self._local_to_global(lidx)

@@ -55,11 +55,17 @@ class MatchBatcher:
                     )
                     self._thread.start()
 
-    def match(self, signature_text: str, failure_type: Optional[str] = None):
+    def match(
+        self,
+        signature_text: str,
+        failure_type: Optional[str] = None,
+        filter_first: bool = False,
+    ):
         self._ensure_thread()
         item: Dict[str, Any] = {
             "text": signature_text,
             "ftype": failure_type,
+            "first": filter_first,
             "ev": threading.Event(),
             "res": None,
             "err": None,
@@ -80,8 +86,11 @@ class MatchBatcher:
                 except queue.Empty:
                     break
             try:
+                first = [b["first"] for b in batch]
+                # an all-unset batch makes the call it always made
+                extra = {"filter_first": first} if any(first) else {}
                 results = self.engine.match_batch(
-                    [b["text"] for b in batch], [b["ftype"] for b in batch]
+                    [b["text"] for b in batch], [b["ftype"] for b in batch], **extra
                 )
                 for b, r in zip(batch, results):
                     b["res"] = r
@@ -159,9 +168,17 @@ def create_app(
         from kakveda_amd.core.metrics import observe_gfkb
 
         if batcher is not None:
-            matches = batcher.match(req.signature_text, failure_type=req.failure_type)
+            matches = batcher.match(
+                req.signature_text,
+                failure_type=req.failure_type,
+                filter_first=req.filter_first,
+            )
         else:
-            matches = engine.match(req.signature_text, failure_type=req.failure_type)
+            matches = engine.match(
+                req.signature_text,
+                failure_type=req.failure_type,
+                filter_first=req.filter_first,
+            )
         observe_gfkb(engine.store.count, len(engine.failures))
         return FailureMatchResponse(matches=matches)
 

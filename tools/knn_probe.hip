@@ -94,7 +94,8 @@ int main(int argc, char** argv) {
       hipLaunchKernelGGL(e.k128, dim3(c128.nchunks, c128.row_tiles),
                          dim3(THREADS), 0, 0, Q, C, pscore, pidx, B, (int)N, D,
                          c128.chunk_tiles, c128.nchunks, rowthr,
-                         (unsigned long long*)nullptr);
+                         (unsigned long long*)nullptr, (const int*)nullptr,
+                         (const int*)nullptr);  // no label filter
     else
       hipLaunchKernelGGL(e.k8p, dim3(c8p.nchunks, c8p.row_tiles),
                          dim3(THREADS8), 0, 0, Q, C, pscore, pidx, B, (int)N, D,
