@@ -80,16 +80,15 @@ Partial8pFn partial8p_kernel(int mode) {
   TORCH_CHECK(false, "no 256x256 kernel for EPI_MODE ", mode);
 }
 
-// cand/ccount/cap/estash are the emission epilogue's (modes 9/15) and
-// null/0 otherwise.
+// eseg/esegcnt/segcap are the emission epilogue's record segments (modes
+// 9/15) and null/0 otherwise.
 void launch_partial8p(int mode, dim3 grid, const KnnArgs& a, float* pscore,
                       int* pidx, int chunk_tiles, int nchunks, unsigned* rowthr,
-                      unsigned long long* cand, unsigned* ccount, long cap,
-                      char* estash) {
+                      unsigned long long* eseg, unsigned* esegcnt, long segcap) {
   hipLaunchKernelGGL(partial8p_kernel(mode), grid, dim3(THREADS8), 0, a.stream,
                      a.q, a.c, pscore, pidx, a.B, a.N, a.D, chunk_tiles, nchunks,
-                     rowthr, (unsigned long long*)nullptr, (float*)nullptr, cand,
-                     ccount, cap, estash);
+                     rowthr, (unsigned long long*)nullptr, (float*)nullptr, eseg,
+                     esegcnt, segcap, (char*)nullptr);
 }
 
 torch::Tensor new_rowthr(const KnnArgs& a) {
@@ -102,13 +101,16 @@ torch::Tensor new_rowthr(const KnnArgs& a) {
 // Emission floors: a prepass over the first PRE_TILES*preg column tiles
 // writes a COMPACT [B][preg][KMAX] partial buffer of its own (so the floor
 // merge scans only what the prepass produced); topk_merge folds it into the
-// exact top-8 of the whole sampled column set, whose 8th is published as
-// the per-row emission threshold (see publish_emission_floor).
+// exact top-8 of the whole sampled column set, whose k-th (k <= KMAX, the
+// caller's floor depth: KMAX in production, any k from the debug probes)
+// is published as the per-row emission threshold (see
+// publish_emission_floor): the k-th best of a subset lower-bounds the
+// corpus k-th best just as the 8th does, and admits k/8 of the candidates.
 struct Floors {
   torch::Tensor rowthr, samp_s, samp_i;
 };
 
-Floors run_emission_floors(const KnnArgs& a, int preg, int prepass_mode,
+Floors run_emission_floors(const KnnArgs& a, int preg, int prepass_mode, int k,
                            Filter flt = {}) {
   Floors f{new_rowthr(a), torch::empty({(long)a.B, (long)KMAX}, a.f32()),
            torch::empty({(long)a.B, (long)KMAX}, a.i64())};
@@ -120,9 +122,9 @@ Floors run_emission_floors(const KnnArgs& a, int preg, int prepass_mode,
                     ppre_s.data_ptr<float>(), ppre_i.data_ptr<int>(), PRE_TILES,
                     preg, (unsigned*)f.rowthr.data_ptr<int>(), flt);
   // (filtered: the sample lists hold eligible columns only, so the floor
-  // published below is the 8th best ELIGIBLE sampled score; with fewer than
-  // 8 eligible samples nothing is published and the main launch emits
-  // every eligible row)
+  // published below is the k-th best ELIGIBLE sampled score; with fewer
+  // than k eligible samples that slot is still -inf, nothing is published
+  // and the main launch emits every eligible row)
   // block-per-row merge: the thread-per-row variant serial-scanned 2k
   // entries per thread (0.9 ms/step at preg=256)
   hipLaunchKernelGGL(topk_merge, dim3(a.B), dim3(THREADS), 0, a.stream,
@@ -131,31 +133,52 @@ Floors run_emission_floors(const KnnArgs& a, int preg, int prepass_mode,
                      (long*)f.samp_i.data_ptr<int64_t>(), preg, KMAX);
   hipLaunchKernelGGL(publish_emission_floor, dim3((a.B + 255) / 256), dim3(256),
                      0, a.stream, f.samp_s.data_ptr<float>(),
-                     (unsigned*)f.rowthr.data_ptr<int>(), a.B, KMAX - 1);
+                     (unsigned*)f.rowthr.data_ptr<int>(), a.B,
+                     std::min(k, KMAX) - 1);
   return f;
 }
 
-// Emission outputs: per-row candidate buffer + counts, and the per-(block,
-// wave) global stash of the 8p cold path (see kernels_impl.h EPI_MODE 9).
+// Emission outputs: per-row candidate buffer + counts. The 8p main kernel
+// (seg > 0) also gets one record segment and one record count per block
+// (see kernels_impl.h EPI_MODE 9 and emit_bin); every block writes its
+// count, so neither needs clearing.
 struct EmitBufs {
-  torch::Tensor cand, ccount, estash;
+  torch::Tensor cand, ccount, eseg, esegcnt;
 };
 
-EmitBufs new_emit_bufs(const KnnArgs& a, long cap, const Chunking& ch) {
-  return {torch::empty({(long)a.B, cap}, a.i64()), torch::zeros({a.B}, a.i32()),
-          torch::empty({(long)ch.nchunks * ch.row_tiles * 8 * ESTASH_STRIDE},
-                       torch::TensorOptions().dtype(torch::kUInt8).device(a.dev))};
+EmitBufs new_emit_bufs(const KnnArgs& a, long cap, const Chunking& ch,
+                       long seg = 0) {
+  EmitBufs e{torch::empty({(long)a.B, cap}, a.i64()),
+             torch::zeros({a.B}, a.i32()), {}, {}};
+  if (seg > 0) {
+    const long blocks = (long)ch.nchunks * ch.row_tiles;
+    e.eseg = torch::empty({blocks, seg}, a.i64());
+    e.esegcnt = torch::empty({blocks}, a.i32());
+  }
+  return e;
 }
 
+// The 8p emission main launch and its binning step: afterwards cand/ccount
+// hold what the per-row scatter of earlier versions left there (candidate
+// order within a row apart, which emit_merge_topk does not depend on).
 void launch_emit8p(int mode, const KnnArgs& a, const Chunking& ch,
                    torch::Tensor& pscore, torch::Tensor& pidx,
-                   const torch::Tensor& rowthr, EmitBufs& e, long cap) {
+                   const torch::Tensor& rowthr, EmitBufs& e, long cap,
+                   long seg) {
+  TORCH_CHECK(seg > 0 && ch.chunk_tiles <= 128,
+              "emission segments need seg > 0 and chunk_tiles <= 128");
+  unsigned long long* const eseg = (unsigned long long*)e.eseg.data_ptr<int64_t>();
+  unsigned* const esegcnt = (unsigned*)e.esegcnt.data_ptr<int>();
   launch_partial8p(mode, dim3(ch.nchunks, ch.row_tiles), a,
                    pscore.data_ptr<float>(), pidx.data_ptr<int>(),
                    ch.chunk_tiles, ch.nchunks, (unsigned*)rowthr.data_ptr<int>(),
-                   (unsigned long long*)e.cand.data_ptr<int64_t>(),
-                   (unsigned*)e.ccount.data_ptr<int>(), cap,
-                   (char*)e.estash.data_ptr<uint8_t>());
+                   eseg, esegcnt, seg);
+  hipLaunchKernelGGL(emit_bin, dim3(ch.nchunks, ch.row_tiles), dim3(256), 0,
+                     a.stream, (const unsigned long long*)eseg,
+                     (const unsigned*)esegcnt, (int)seg, ch.chunk_tiles,
+                     ch.nchunks, a.B, a.N,
+                     (unsigned long long*)e.cand.data_ptr<int64_t>(),
+                     (unsigned*)e.ccount.data_ptr<int>(), cap);
 }
 
 std::tuple<torch::Tensor, torch::Tensor> cosine_topk_impl(
@@ -175,10 +198,21 @@ std::tuple<torch::Tensor, torch::Tensor> cosine_topk_impl(
   if (p.merge == MergeKernel::Emit) {
     // candidates go to a per-row global buffer sized for ~8N/sample
     // expected emissions with ~25x headroom
-    const Floors f = p.prepass
-                         ? run_emission_floors(a, p.preg, p.prepass_mode, flt)
-                         : Floors{new_rowthr(a), {}, {}};
-    EmitBufs e = new_emit_bufs(a, p.cap, ch);
+    // Floor depth: the 8th best of the sample for every k. Publishing the
+    // request's k-th best instead is as exact under the 8p main kernel
+    // (its scores are bit-equal to the prepass kernel's) and cuts the
+    // candidates to k/8, but measured +0.8..1.4% on the 10M bench, inside
+    // the run-to-run band in two of three A/B sets, so it does not ship
+    // (profiles/knn_kernel_history.md). It must never reach the unfiltered
+    // streaming kernels: they sum in another order, may score the column
+    // that set the floor an ulp lower, and rely on the slack between the
+    // 8th and the k-th best (k < 8) to keep it.
+    const int floor_k = KMAX;
+    const Floors f =
+        p.prepass
+            ? run_emission_floors(a, p.preg, p.prepass_mode, floor_k, flt)
+            : Floors{new_rowthr(a), {}, {}};
+    EmitBufs e = new_emit_bufs(a, p.cap, ch, p.seg);
     if (p.main == MainKernel::SmallB && flt) {
       hipLaunchKernelGGL(smallb_emit_kernel_v4<true>, dim3(p.smallb_blocks),
                          dim3(256), (size_t)B * a.D * 2, a.stream, a.q, a.c, B,
@@ -206,7 +240,7 @@ std::tuple<torch::Tensor, torch::Tensor> cosine_topk_impl(
                            (unsigned*)e.ccount.data_ptr<int>(), p.cap,
                            (const int*)nullptr, (const int*)nullptr);
     } else {
-      launch_emit8p(p.mode, a, ch, pscore, pidx, f.rowthr, e, p.cap);
+      launch_emit8p(p.mode, a, ch, pscore, pidx, f.rowthr, e, p.cap, p.seg);
     }
     hipLaunchKernelGGL(emit_merge_topk, dim3(B), dim3(256), 0, a.stream,
                        (const unsigned long long*)e.cand.data_ptr<int64_t>(),
@@ -217,10 +251,14 @@ std::tuple<torch::Tensor, torch::Tensor> cosine_topk_impl(
     // an overflowed row means emission skipped stores — rerun the whole
     // batch through the list-epilogue production kernel
     const long mx = (long)e.ccount.max().item<int>();
-    if (env.emit_debug)
+    if (env.emit_debug) {
       printf("emit: rows=%d max=%ld mean=%.1f cap=%ld%s\n", B, mx,
              e.ccount.to(torch::kFloat32).mean().item<float>(), p.cap,
              mx > p.cap ? "  FALLBACK" : "");
+      if (p.seg > 0)
+        printf("emit: segments=%ld max=%d seg=%ld\n", (long)e.esegcnt.size(0),
+               e.esegcnt.max().item<int>(), p.seg);
+    }
     if (mx > p.cap) {
       static bool warned = false;
       if (!warned) {
@@ -251,7 +289,7 @@ std::tuple<torch::Tensor, torch::Tensor> cosine_topk_impl(
   if (p.main == MainKernel::Stash8p)
     launch_partial8p(p.mode, grid, a, pscore.data_ptr<float>(),
                      pidx.data_ptr<int>(), ch.chunk_tiles, ch.nchunks, thr,
-                     nullptr, nullptr, 0, nullptr);
+                     nullptr, nullptr, 0);
   else  // List128, or Argmax128 (k=1: per-row max, no thresholds)
     launch_partial128(p.mode, grid, a, pscore.data_ptr<float>(),
                       pidx.data_ptr<int>(), ch.chunk_tiles, ch.nchunks,
@@ -430,32 +468,37 @@ std::tuple<torch::Tensor, torch::Tensor> kmeans_update(
 }
 
 std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> floor_probe(
-    torch::Tensor queries, torch::Tensor corpus, int64_t pregq) {
+    torch::Tensor queries, torch::Tensor corpus, int64_t pregq, int64_t k) {
   // Debug: run ONLY the emission floor pipeline (prepass -> compact
   // partials -> merge -> publish) and return (samp_s [B,KMAX], samp_i,
-  // rowthr u32 [B]) for offline comparison against a torch reference.
+  // rowthr u32 [B]) for offline comparison against a torch reference. The
+  // published floor is the k-th best of the sample (k = 8: the deepest).
   check_bf16_2d(queries, "queries");
   check_bf16_2d(corpus, "corpus");
   const KnnArgs a = knn_args(queries, corpus, (int)corpus.size(0));
-  const Floors f = run_emission_floors(a, ((int)pregq) & ~7, 11);
+  TORCH_CHECK(k >= 1 && k <= KMAX, "k must be in [1,", KMAX, "]");
+  const Floors f = run_emission_floors(a, ((int)pregq) & ~7, 11, (int)k);
   return {f.samp_s, f.samp_i, f.rowthr};
 }
 
 std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> emit_counts_probe(
-    torch::Tensor queries, torch::Tensor corpus, int64_t pregq) {
-  // Debug: run floors + the mode-9 emission kernel and return the raw
-  // per-row candidate counts (no merge, no fallback) for offline
-  // inspection of which rows overcount.
+    torch::Tensor queries, torch::Tensor corpus, int64_t pregq, int64_t k) {
+  // Debug: run floors (k-th best of the sample) + the mode-9 emission
+  // kernel + the binning step and return the raw per-row candidate counts
+  // and candidates (no merge, no fallback) for offline inspection of which
+  // rows overcount.
   check_bf16_2d(queries, "queries");
   check_bf16_2d(corpus, "corpus");
   const KnnArgs a = knn_args(queries, corpus, (int)corpus.size(0));
-  const Floors f = run_emission_floors(a, ((int)pregq) & ~7, 11);
+  TORCH_CHECK(k >= 1 && k <= KMAX, "k must be in [1,", KMAX, "]");
+  const Floors f = run_emission_floors(a, ((int)pregq) & ~7, 11, (int)k);
   const Chunking ch = chunking(a.B, a.N, BM8, default_target(BM8));
   const long CAP = 32768;
+  const long seg = emit_seg_cap(a.B, CAP, ch, 0);
   auto pscore = torch::empty({(long)a.B * ch.nchunks * KMAX}, a.f32());
   auto pidx = torch::empty({(long)a.B * ch.nchunks * KMAX}, a.i32());
-  EmitBufs e = new_emit_bufs(a, CAP, ch);
-  launch_emit8p(9, a, ch, pscore, pidx, f.rowthr, e, CAP);
+  EmitBufs e = new_emit_bufs(a, CAP, ch, seg);
+  launch_emit8p(9, a, ch, pscore, pidx, f.rowthr, e, CAP, seg);
   return {e.ccount, e.cand, f.rowthr};
 }
 
@@ -479,8 +522,7 @@ double probe8p(torch::Tensor queries, torch::Tensor corpus, int64_t mode,
   auto launch = [&] {
     launch_partial8p((int)mode, dim3(ch.nchunks, ch.row_tiles), a,
                      pscore.data_ptr<float>(), pidx.data_ptr<int>(),
-                     ch.chunk_tiles, ch.nchunks, nullptr, nullptr, nullptr, 0,
-                     nullptr);
+                     ch.chunk_tiles, ch.nchunks, nullptr, nullptr, nullptr, 0);
   };
   launch();  // warmup
   hipEvent_t e0, e1;
@@ -507,8 +549,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("kmeans_assign", &kmeans_assign,
         "argmax-cosine assignment, LDS-resident centroids (C<=64)");
   m.def("probe8p", &probe8p, "8p epilogue-isolation timing probe");
-  m.def("floor_probe", &floor_probe, "emission floor pipeline debug probe");
+  m.def("floor_probe", &floor_probe, "emission floor pipeline debug probe",
+        pybind11::arg("queries"), pybind11::arg("corpus"),
+        pybind11::arg("pregq"), pybind11::arg("k") = (int64_t)KMAX);
   m.def("emit_counts_probe", &emit_counts_probe,
-        "emission per-row count debug probe");
+        "emission per-row count debug probe", pybind11::arg("queries"),
+        pybind11::arg("corpus"), pybind11::arg("pregq"),
+        pybind11::arg("k") = (int64_t)KMAX);
   m.attr("KMAX") = KMAX;
 }

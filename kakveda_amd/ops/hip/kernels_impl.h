@@ -601,7 +601,8 @@ __global__ __launch_bounds__(THREADS, 2) void cosine_topk_partial_t(
 //   Prologue: A(0), B(0), B(1) certified by vmcnt(0) + __syncthreads
 //     before either group's first read.
 //   lsc/lix lists: written before the first __syncthreads, read after the
-//     final barrier (modes 1, 15, 16); never touched in between.
+//     final barrier (modes 1, 16); never touched in between. The emission
+//     modes (9, 12, 15) have no lists: see the emission ledger below.
 // Mode 6 keeps lockstep: its stash/drain epilogue shares LDS and barriers
 // across both groups. Mode 16 is mode 1 on the lockstep schedule, kept so
 // probe8p can A/B the two sync structures in one process.
@@ -614,55 +615,66 @@ __global__ __launch_bounds__(THREADS, 2) void cosine_topk_partial_t(
 //
 // LDS: 2 buffers x (A[2 halves] + B[2 halves]) x 16 KiB = 128 KiB
 // + shared top-k lists 16 KiB = 144 KiB -> 1 block/CU, 2 waves/SIMD.
+// Emission modes: 128 KiB + 8 wave stashes x 3 KiB + cursor = 152 KiB.
+//
+// Emission ledger (modes 9, 15; the cold path of the epilogue):
+//   (a) Stash bytes vs staging images. Every glds destination is
+//     ahalf(b,h) or bhalf(b,h) + an offset < HALF8, i.e. a byte in
+//     [0, 8*HALF8) = [0, 131072). Wave w's stash is [131072 + 3072w,
+//     131072 + 3072(w+1)), the cursor word is at 131072 + 24576: both past
+//     the last image byte in every window, so no staging write or fragment
+//     read can touch them. A stash slice is written and read by its own
+//     wave only (LDS serves one wave's accesses in issue order; the reads'
+//     results are awaited on lgkmcnt), so it needs no barrier and the
+//     staggered groups stay legal. The cursor is shared by the 8 waves
+//     through a returning LDS add; it is zeroed before the first
+//     __syncthreads and read after the last one.
+//   (b) Fire-and-forget record stores vs the counted wait. vmcnt counts
+//     loads and stores alike, and loads retire in issue order among
+//     themselves. At window t ph3 the newest four LOADS are B(t+2)'s, so
+//     after `vmcnt(4)` at most four operations are outstanding and any
+//     outstanding load is one of those four: A(t+1) and B(t+1) have landed
+//     whatever number of record stores is still in flight. Outstanding
+//     stores only make the wait stricter (fewer B(t+2) loads may remain).
+//     The chunk-tail `vmcnt(0)` drains everything, stores included, once
+//     per block; the block's last `vmcnt(0)` before the count is published
+//     is once per block too. Nothing else in the tile loop waits on vmcnt.
+//   (c) Nothing in this kernel reads a record or a count back: the
+//     segments are consumed by emit_bin, a later launch on the same stream.
 // ===========================================================================
 
 
 constexpr int THREADS8 = 512;
 constexpr int HALF8 = 16384;  // one [128][64] bf16 half-image
-constexpr int EGCAP = 8;          // emission stash slots per (block, wave)
-constexpr int ESTASH_STRIDE = 64 + EGCAP * 1024;  // meta + slots, bytes
+constexpr int EGCAP = 3;  // emission stash slots per wave (1 KiB each)
+constexpr int ESTASH_OFF = 8 * HALF8;        // first byte past the images
+constexpr int ESTASH_WAVE = EGCAP * 1024;    // one wave's stash slice, bytes
+constexpr int ESEG_COL_BITS = 15;  // column within a chunk: chunk_tiles <= 128
 
-// Rare-path drain for the emission epilogue (EPI_MODE 9/15): the cold path
-// stashes qualifying groups' accumulator quads into the wave's private
-// slice of the global emission scratch (plain stores, no calls while the
-// 128 accumulator VGPRs are live), then makes ONE call here per wave per
-// cold tile. By call time the accumulators are dead, so the call costs
-// no spills — earlier structures (per-group callee: 32-reg/tile
-// pre-spill; inlined appends: 0.5-1 KiB/lane scratch) all lost to the
-// acc-liveness-across-append problem. __noinline__ keeps the body out
-// of the sweep's register allocation entirely.
-__device__ __noinline__ void emit_stashed(
-    unsigned long long* __restrict__ cand, unsigned* __restrict__ ccount,
-    long ccap, char* stash, int ng, int rowbase, int colb, int N, int B,
-    float thr0, float thr1) {
-  const int lane = threadIdx.x & 63;
-  const int g = lane >> 4;
-  for (int i = 0; i < ng; ++i) {
-    const int gid = (int)((volatile unsigned*)stash)[i];
-    const int m = gid >> 2, reg = gid & 3;
-    const int rl = m * 16 + g * 4 + reg;
-    const float thr = __shfl(m >= 4 ? thr1 : thr0, rl & 63, 64);
-    const f32x4 v = *(const f32x4*)(stash + 64 + i * 1024 + lane * 16);
-    const int grow = rowbase + rl;
-    const bool q0 = v[0] >= thr && colb < N;
-    const bool q1 = v[1] >= thr && colb + 16 < N;
-    const bool q2 = v[2] >= thr && colb + 32 < N;
-    const bool q3 = v[3] >= thr && colb + 48 < N;
-    const int myc = (int)q0 + (int)q1 + (int)q2 + (int)q3;
-    if (!myc || grow >= B) continue;
-    unsigned pos = atomicAdd(&ccount[grow], (unsigned)myc);
-    unsigned long long* crow = cand + (size_t)grow * ccap;
-#pragma unroll
-    for (int n = 0; n < 4; ++n) {
-      const bool qn = n == 0 ? q0 : n == 1 ? q1 : n == 2 ? q2 : q3;
-      if (qn) {
-        if (pos < (unsigned)ccap)
-          crow[pos] = ((unsigned long long)enc_f32(v[n]) << 32) |
-                      (unsigned)(0x7fffffff - (colb + n * 16));
-        ++pos;
-      }
-    }
-  }
+// Emission record (EPI_MODE 9/15 -> emit_bin): order-encoded score in the
+// high word; row within the 256-row tile and column within the block's
+// chunk in the low word. emit_bin rebuilds (row, global column) from the
+// segment's (row_tile, chunk_id).
+DEVINL unsigned long long eseg_record(float score, int row_in_tile,
+                                      int col_in_chunk) {
+  return ((unsigned long long)enc_f32(score) << 32) |
+         (unsigned)((row_in_tile << ESEG_COL_BITS) | col_in_chunk);
+}
+
+// Returning add on an LDS word, waited for on lgkmcnt alone. Written as
+// asm because the compiler puts a vmcnt(0) in front of an LDS atomic in a
+// kernel that also stages with global_load_lds (it cannot tell the word
+// from a staging destination), which would drain the staging pipeline and
+// the epilogue's own fire-and-forget stores.
+DEVINL unsigned lds_add_rtn(unsigned* word, unsigned v) {
+  const unsigned addr = (unsigned)(__UINTPTR_TYPE__)(
+      __attribute__((address_space(3))) unsigned*)word;
+  unsigned old;
+  asm volatile("ds_add_rtn_u32 %0, %1, %2\n\ts_waitcnt lgkmcnt(0)"
+               : "=&v"(old)
+               : "v"(addr), "v"(v)
+               : "memory");
+  return old;
 }
 
 // EPI_MODE (numbering is historical; the pruned variants and their
@@ -679,8 +691,11 @@ __device__ __noinline__ void emit_stashed(
 //   16 = 1 on the lockstep schedule (probe8p A/B, tools/knn_probe.hip)
 // Modes 1, 9, 12, 15 run their two wave groups staggered by one barrier;
 // 6 and 16 run lockstep (ledger in the block comment above).
-// `stats` and `slab` are unused (they belonged to pruned modes) and stay
-// in the signature so kernel symbols and kernarg offsets do not move.
+// eseg/esegcnt/segcap are the emission modes' record segments (they took
+// the slots, and types, of the per-row candidate buffer the kernel once
+// scattered into itself). `stats`, `slab` and `unused` are unused (they
+// belonged to pruned modes and to the global stash) and stay in the
+// signature so kernel symbols and kernarg offsets do not move.
 template <int EPI_MODE>
 __global__ __launch_bounds__(THREADS8, 2) void cosine_topk_partial8p_t(
     const bf16_t* __restrict__ Q, const bf16_t* __restrict__ C,
@@ -688,15 +703,19 @@ __global__ __launch_bounds__(THREADS8, 2) void cosine_topk_partial8p_t(
     int B, int N, int D, int chunk_tiles, int nchunks,
     unsigned* rowthr = nullptr, unsigned long long* stats = nullptr,
     float* __restrict__ slab = nullptr,
-    unsigned long long* __restrict__ cand = nullptr,
-    unsigned* __restrict__ ccount = nullptr, long ccap = 0,
-    char* __restrict__ estash = nullptr) {
+    unsigned long long* __restrict__ eseg = nullptr,
+    unsigned* __restrict__ esegcnt = nullptr, long segcap = 0,
+    char* __restrict__ unused = nullptr) {
   constexpr bool EMIT = EPI_MODE == 9 || EPI_MODE == 12 || EPI_MODE == 15;
   constexpr bool GEMM_ONLY = EPI_MODE == 1 || EPI_MODE == 16;
   // staggered wave groups: only for the modes whose epilogue has no
-  // barrier and no LDS traffic (see the ledger above the kernel)
+  // barrier and touches no LDS byte another wave reads or stages (see the
+  // ledger above the kernel)
   constexpr bool STAGGER = EPI_MODE == 1 || EMIT;
-  __shared__ char smem[8 * HALF8 + 2 * BM8 * KMAX * 4 + 32];
+  // one array: staging images, then (emission) the wave-private stashes and
+  // the segment cursor, or (other modes) the shared lists and wave flags
+  __shared__ char smem[EMIT ? ESTASH_OFF + 8 * ESTASH_WAVE + 32
+                            : 8 * HALF8 + 2 * BM8 * KMAX * 4 + 32];
   char* const smem0 = smem;
   // buffer b in {0,1}: A half h at b*4*HALF8 + h*HALF8; B half h at +2*HALF8
   auto ahalf = [&](int b, int h) -> char* {
@@ -740,13 +759,35 @@ __global__ __launch_bounds__(THREADS8, 2) void cosine_topk_partial8p_t(
   const int tiles_here = min(chunk_tiles, ntiles_total - tile0);
   const int nkt = D / 64;  // windows per col tile
 
-  for (int i = tid; i < BM8 * KMAX; i += THREADS8) {
-    lsc[i] = NEG_INF;
-    lix[i] = -1;
+  // emission append state (modes 9/15): this wave's stash slice, the
+  // block's record cursor (an LDS word behind the stashes) and the block's
+  // segment of the global record buffer, indexed by (row_tile, chunk_id)
+  constexpr bool APPEND = EPI_MODE == 9 || EPI_MODE == 15;
+  // (lambdas: the other modes' instruction streams must not see them)
+  auto estash = [&]() -> char* {
+    return smem0 + ESTASH_OFF + wid * ESTASH_WAVE;
+  };
+  auto ecursor = [&]() -> unsigned* {
+    return (unsigned*)(smem0 + ESTASH_OFF + 8 * ESTASH_WAVE);
+  };
+  auto segid = [&]() -> size_t {
+    return (size_t)row_tile * nchunks + chunk_id;
+  };
+
+  if constexpr (EMIT) {
+    if (tid == 0) *ecursor() = 0u;
+  } else {
+    for (int i = tid; i < BM8 * KMAX; i += THREADS8) {
+      lsc[i] = NEG_INF;
+      lix[i] = -1;
+    }
   }
   __syncthreads();
   if (tiles_here <= 0) {
-    // padded chunk: emit -inf partials and exit
+    // padded chunk: emit -inf partials (and an empty segment) and exit
+    if constexpr (APPEND) {
+      if (tid == 0) esegcnt[segid()] = 0u;
+    }
     if (tid < BM8 && row0 + tid < B) {
       const size_t base = ((size_t)(row0 + tid) * nchunks + chunk_id) * KMAX;
 #pragma unroll
@@ -816,7 +857,7 @@ __global__ __launch_bounds__(THREADS8, 2) void cosine_topk_partial8p_t(
   // becomes a pure-VALU running max-diff with a single ballot.
   // Exactness: qualification vs the rounded-DOWN floor is a superset of
   // qualification vs the exact floor, and a hot-sweep positive only opens
-  // the cold path, whose per-lane compares in emit_stashed re-check the
+  // the cold path, whose per-lane compares in the drain re-check the
   // EXACT thr0/thr1 before any candidate is stored.
   unsigned tvp[16];
   if constexpr (EPI_MODE == 15) {
@@ -848,18 +889,31 @@ __global__ __launch_bounds__(THREADS8, 2) void cosine_topk_partial8p_t(
       }
   }
 
+  // per-lane threshold floors for this wave-half's two rows (rows beyond
+  // B get +inf so clamped-row garbage never flags). The emission modes
+  // read them ONCE per block: under their launch rowthr is static (the
+  // prepass has finished and modes 9/12/15 never write it). Read per tile,
+  // each of the two loads cost an L2 round trip behind a vmcnt(0) that also
+  // drained the B(t+2) staging the counted wait keeps in flight. Mode 6
+  // publishes into rowthr during its launch and keeps the per-tile read.
+  auto load_floors = [&](float& t0, float& t1) {
+    const int r0g = row0 + wr * 128 + lane;
+    t0 = (r0g < B) ? (rowthr ? dec_f32(rowthr[r0g]) : NEG_INF) : 1e38f;
+    t1 = (r0g + 64 < B) ? (rowthr ? dec_f32(rowthr[r0g + 64]) : NEG_INF)
+                        : 1e38f;
+  };
+  float thr0 = NEG_INF, thr1 = NEG_INF;
+  if constexpr (EMIT) {
+    load_floors(thr0, thr1);
+    // a use here, right behind the prologue's full drain: the compiler's
+    // wait for the two loads lands before the tile loop, not inside it
+    asm volatile("" ::"v"(thr0), "v"(thr1));
+  }
+
   for (int j = 0; j < tiles_here; ++j) {
     const int col0 = (tile0 + j) * BN8;
 
-    // per-lane threshold floors for this wave-half's two rows (rows
-    // beyond B get +inf so clamped-row garbage never flags)
-    float thr0 = NEG_INF, thr1 = NEG_INF;
-    if constexpr (!GEMM_ONLY) {
-      const int r0g = row0 + wr * 128 + lane;
-      thr0 = (r0g < B) ? (rowthr ? dec_f32(rowthr[r0g]) : NEG_INF) : 1e38f;
-      thr1 = (r0g + 64 < B) ? (rowthr ? dec_f32(rowthr[r0g + 64]) : NEG_INF)
-                            : 1e38f;
-    }
+    if constexpr (!GEMM_ONLY && !EMIT) load_floors(thr0, thr1);
 
     f32x4 acc[8][4];
 #pragma unroll
@@ -964,25 +1018,24 @@ __global__ __launch_bounds__(THREADS8, 2) void cosine_topk_partial8p_t(
         for (int n = 0; n < 4; ++n)
           asm volatile("" ::"v"(acc[m][n]));
     } else if constexpr (EMIT) {
-      // ---- threshold-emission epilogue (round 2): no lists, no stash
-      // phases, no barriers — the 1017 TF GEMM core's full accumulator
-      // sweep is a register compare + rare global append. Exactness: the
-      // rowthr floors are prepass-published 8-deep list minima, i.e. the
-      // 8th-best of a score SUBSET, which lower-bounds the corpus
-      // 8th-best and hence the true k-th for any k <= 8 — so emitting
-      // every score >= floor provably captures the whole top-k. The
-      // companion emit_merge_topk kernel reduces the (expected ~8N/s per
-      // row) candidates; per-row counts above ccap flag a host fallback.
-      // pack (order-encoded score << 32) | (0x7fffffff - col): one u64
-      // max = higher score, then lower col (torch tie-break).
+      // ---- threshold-emission epilogue: no lists, no stash phases, no
+      // barriers — the GEMM core's full accumulator sweep is a register
+      // compare + rare record append. Exactness: the rowthr floors are
+      // the 8th best of a score SUBSET, which lower-bounds the corpus
+      // 8th best and hence the true k-th for any k <= 8 — so emitting
+      // every score >= floor provably captures the whole top-k. emit_bin
+      // scatters the records into the per-row candidate buffer and
+      // emit_merge_topk reduces the (expected ~8N/s per row) candidates
+      // (a j-th-best floor, j >= k, is as exact and admits j/8 of them:
+      // publish_emission_floor takes the depth); per-row counts
+      // above the cap, or an overflowed segment, flag a host fallback.
       // Two-phase sweep: the HOT pass is pure compare/shfl/ballot with
       // NO call sites, so the compiler keeps the 128 accumulator VGPRs
       // unspilled (a single-pass sweep with per-group calls pre-spilled
       // 32 regs per tile per wave -> ~27 GB of scratch traffic at the
-      // 10M bench, the measured 917-vs-1017 TF gap). The COLD pass
-      // (wave-uniform qmask != 0, ~12% of tiles per wave) stashes the
-      // qualifying groups and makes the rare __noinline__ emit_stashed
-      // call; its spills live in that cold block only.
+      // 10M bench). The COLD pass (wave-uniform qmask != 0, ~12% of tiles
+      // per wave) stashes the qualifying groups in LDS and drains them
+      // inline at ONE site, so no call and no spill either.
       const int colb = col0 + wc * 64 + cl;
       unsigned qm32 = 0;
       if constexpr (EPI_MODE == 15) {
@@ -1035,48 +1088,83 @@ __global__ __launch_bounds__(THREADS8, 2) void cosine_topk_partial8p_t(
         asm volatile("" ::"s"(qm32));
       } else {
         if (__builtin_expect(qm32 != 0, 0)) {  // uniform cold path
-          // stash qualifying groups into this (block, wave)'s private
-          // slice of the GLOBAL emission scratch. An LDS stash in the
-          // "dead" last-window A-image corrupted later tiles' scores
-          // (isolated by an A/B against a stash-free cold path —
-          // the image interacts with the cross-tile staging pipeline in
-          // a way the stash-phase epilogues' barrier discipline tolerates
-          // but a late per-wave write does not); global scratch has no
-          // aliasing with the pipeline at all and needs no barrier.
-          char* stash =
-              estash +
-              ((size_t)(blockIdx.x + (size_t)gridDim.x * blockIdx.y) * 8 +
-               wid) *
-                  ESTASH_STRIDE;
-          int ng = 0;
+          // Nothing here waits on global memory. Qualifying groups'
+          // accumulator quads go to this wave's private LDS stash slice
+          // (bytes no staging image ever covers: ledger item (a) above the
+          // kernel), written and read back by the same wave, ordered by
+          // lgkmcnt alone. The drain compares against the EXACT floors,
+          // compacts the qualifying lanes with ballot + mbcnt and appends
+          // 8-byte records to the block's segment with plain stores; the
+          // segment cursor is an LDS word. The stores are never waited
+          // for and never read back by this kernel (ledger (b), (c)).
+          // An LDS stash in the "dead" last-window A image once corrupted
+          // later tiles' scores (cause never found), so no staging byte
+          // is aliased in any window.
+          // Correlated query batches (e.g. the bench's template-generated
+          // signatures) make qualifying groups BURST on "hot" corpus tiles
+          // (dozens of groups at once), so a full stash drains and
+          // refills: the stash+drain pass repeats until no group is left.
+          const int rowl0 = wr * 128;                 // row within the tile
+          const int colc = j * BN8 + wc * 64 + cl;    // column within chunk
+          unsigned long long* const seg = eseg + segid() * (size_t)segcap;
+          char* const st = estash();
+          unsigned rem = qm32;
+          do {
+            int ng = 0;
+            unsigned gids = 0;  // 5 bits of (m*4+reg) per stashed slot
 #pragma unroll
-          for (int m = 0; m < 8; ++m) {
+            for (int m = 0; m < 8; ++m) {
 #pragma unroll
-            for (int reg = 0; reg < 4; ++reg) {
-              if (!(qm32 & (1u << (m * 4 + reg)))) continue;
-              if (__builtin_expect(ng == EGCAP, 0)) {
-                // stash full. Correlated query batches (e.g. the bench's
-                // template-generated signatures) make qualifying groups
-                // BURST on "hot" corpus tiles — dozens of groups at once
-                // — so overflow must drain-and-refill, not bail (a
-                // poison->host-fallback here fired ~600x/row-tile on the
-                // bench and doubled the step). This mid-sweep call keeps
-                // some accumulators live (cold-block spills only).
-                emit_stashed(cand, ccount, ccap, stash, ng,
-                             row0 + wr * 128, colb, N, B, thr0, thr1);
-                ng = 0;
+              for (int reg = 0; reg < 4; ++reg) {
+                const unsigned bit = 1u << (m * 4 + reg);
+                if ((rem & bit) && ng < EGCAP) {
+                  *(f32x4*)(st + ng * 1024 + lane * 16) =
+                      f32x4{acc[m][0][reg], acc[m][1][reg], acc[m][2][reg],
+                            acc[m][3][reg]};
+                  gids |= (unsigned)(m * 4 + reg) << (5 * ng);
+                  rem &= ~bit;
+                  ++ng;
+                }
               }
-              *(f32x4*)(stash + 64 + ng * 1024 + (size_t)lane * 16) =
-                  f32x4{acc[m][0][reg], acc[m][1][reg], acc[m][2][reg],
-                        acc[m][3][reg]};
-              if (lane == 0)
-                ((volatile unsigned*)stash)[ng] = (unsigned)(m * 4 + reg);
-              ++ng;
             }
-          }
-          if (ng > 0)
-            emit_stashed(cand, ccount, ccap, stash, ng, row0 + wr * 128,
-                         colb, N, B, thr0, thr1);
+            for (int i = 0; i < ng; ++i) {
+              const int gid = (int)((gids >> (5 * i)) & 31u);
+              const int m = gid >> 2, reg = gid & 3;
+              const int rl = m * 16 + g * 4 + reg;  // 0..127 within the half
+              const float thr = __shfl(m >= 4 ? thr1 : thr0, rl & 63, 64);
+              const f32x4 v = *(const f32x4*)(st + i * 1024 + lane * 16);
+              const bool rowok = row0 + rowl0 + rl < B;
+              const bool q0 = rowok && v[0] >= thr && colb < N;
+              const bool q1 = rowok && v[1] >= thr && colb + 16 < N;
+              const bool q2 = rowok && v[2] >= thr && colb + 32 < N;
+              const bool q3 = rowok && v[3] >= thr && colb + 48 < N;
+              const unsigned long long b0 = __ballot(q0), b1 = __ballot(q1),
+                                       b2 = __ballot(q2), b3 = __ballot(q3);
+              const unsigned c0 = __popcll(b0), c1 = __popcll(b1),
+                             c2 = __popcll(b2), c3 = __popcll(b3);
+              const unsigned total = c0 + c1 + c2 + c3;
+              if (total == 0) continue;  // uniform
+              unsigned base = 0;
+              if (lane == 0) base = lds_add_rtn(ecursor(), total);
+              base = (unsigned)__builtin_amdgcn_readfirstlane((int)base);
+              // a segment that would overflow stops storing; the cursor
+              // keeps the true count and emit_bin poisons the row tile
+              auto put = [&](bool q, unsigned long long bal, unsigned off,
+                             float sc, int n) {
+                const unsigned pos =
+                    base + off +
+                    __builtin_amdgcn_mbcnt_hi(
+                        (unsigned)(bal >> 32),
+                        __builtin_amdgcn_mbcnt_lo((unsigned)bal, 0u));
+                if (q && pos < (unsigned)segcap)
+                  seg[pos] = eseg_record(sc, rowl0 + rl, colc + n * 16);
+              };
+              put(q0, b0, 0u, v[0], 0);
+              put(q1, b1, c0, v[1], 1);
+              put(q2, b2, c0 + c1, v[2], 2);
+              put(q3, b3, c0 + c1 + c2, v[3], 3);
+            }
+          } while (rem != 0);
         }
       }
     } else {
@@ -1208,10 +1296,17 @@ __global__ __launch_bounds__(THREADS8, 2) void cosine_topk_partial8p_t(
     }
   }
 
+  // emission: publish the segment's true record count (it may exceed
+  // segcap: emit_bin then poisons the row tile). Every wave's cursor
+  // atomics returned before its last readfirstlane, and both wave groups
+  // have executed the same number of barriers by now.
+  if constexpr (APPEND) {
+    __syncthreads();
+    if (tid == 0) esegcnt[segid()] = *ecursor();
+  }
   // write partials: [B][nchunks][KMAX] (emission modes have no lists —
-  // their results went straight to the candidate buffer; mode 15 still
-  // writes its untouched -inf lists, which nothing reads)
-  if constexpr (EPI_MODE != 9 && EPI_MODE != 12) {
+  // their results went to the record segments)
+  if constexpr (!EMIT) {
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
     if (tid < BM8) {
@@ -1243,6 +1338,45 @@ __global__ void publish_emission_floor(const float* __restrict__ merged_s,
   if (r < B) {
     const float v = merged_s[(size_t)r * KMAX + kth];
     if (v > NEG_INF) atomicMax(&rowthr[r], enc_f32(v));
+  }
+}
+
+// ---------------------------------------------------------------------------
+// Binning step of the 8-phase emission path: one block per record segment
+// (grid = (nchunks, row_tiles), the main launch's logical block ids).
+// Rebuilds (row, global column) of every record and scatters the packed
+// (order-encoded score << 32) | (0x7fffffff - col) into the per-row
+// candidate buffer emit_merge_topk reads. The per-row atomics live here,
+// off the GEMM kernel's critical path. A segment whose true count exceeds
+// its capacity lost records: it poisons one ccount of its row tile past
+// ccap, which the host's single ccount.max() readback turns into the loud
+// fallback, exactly as a per-row overflow does.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void emit_bin(
+    const unsigned long long* __restrict__ eseg,
+    const unsigned* __restrict__ esegcnt, int segcap, int chunk_tiles,
+    int nchunks, int B, int N, unsigned long long* __restrict__ cand,
+    unsigned* __restrict__ ccount, long ccap) {
+  const int chunk_id = blockIdx.x, row_tile = blockIdx.y;
+  const size_t segid = (size_t)row_tile * nchunks + chunk_id;
+  const unsigned cnt = esegcnt[segid];
+  if (cnt == 0) return;
+  const int row0 = row_tile * BM8;
+  const int colbase = chunk_id * chunk_tiles * BN8;
+  if (cnt > (unsigned)segcap && threadIdx.x == 0)
+    atomicAdd(&ccount[row0], (unsigned)ccap + 1u);
+  const unsigned n = min(cnt, (unsigned)segcap);
+  const unsigned long long* seg = eseg + segid * (size_t)segcap;
+  for (unsigned i = threadIdx.x; i < n; i += 256) {
+    const unsigned long long rec = seg[i];
+    const unsigned lo = (unsigned)rec;
+    const int row = row0 + (int)(lo >> ESEG_COL_BITS);
+    const int col = colbase + (int)(lo & ((1u << ESEG_COL_BITS) - 1u));
+    if (row >= B || col >= N) continue;  // never emitted; guards the stores
+    const unsigned pos = atomicAdd(&ccount[row], 1u);
+    if (pos < (unsigned)ccap)
+      cand[(size_t)row * ccap + pos] =
+          (rec & 0xffffffff00000000ull) | (unsigned)(0x7fffffff - col);
   }
 }
 

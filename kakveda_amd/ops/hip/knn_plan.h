@@ -36,6 +36,7 @@ struct KnnEnv {
   int preg = 0;                  // KAKVEDA_KNN_PREG (<= 0: default)
   long target = 0;               // KAKVEDA_KNN_TARGET (<= 0: default)
   long cap = 32768;              // KAKVEDA_KNN_EMIT_CAP
+  long seg = 0;                  // KAKVEDA_KNN_EMIT_SEG (<= 0: default)
   bool emit_debug = false;       // KAKVEDA_KNN_EMIT_DEBUG=1
 };
 
@@ -69,6 +70,7 @@ KnnEnv parse_knn_env(GetEnv&& get) {
   if ((v = get("KAKVEDA_KNN_PREG"))) e.preg = (int)std::atol(v);
   if ((v = get("KAKVEDA_KNN_TARGET"))) e.target = std::atol(v);
   if ((v = get("KAKVEDA_KNN_EMIT_CAP"))) e.cap = std::atol(v);
+  if ((v = get("KAKVEDA_KNN_EMIT_SEG"))) e.seg = std::atol(v);
   if ((v = get("KAKVEDA_KNN_EMIT_DEBUG"))) e.emit_debug = v[0] == '1';
   return e;
 }
@@ -95,6 +97,25 @@ inline Chunking chunking(int B, int N, int tile, long target) {
   return c;
 }
 
+// Emission record segments (8-phase emission main kernel): each block
+// appends its 8-byte candidate records to a private segment of `seg`
+// records; the binning kernel scatters them into the per-row candidate
+// buffer. Default capacity: the bench shape (10M x 768, B = 2048, k = 5)
+// measured 542 records in the fullest of its 2496 blocks (mean ~260), so
+// 8192 is 15x headroom. The segments never take more memory than the
+// candidate buffer beside them (both hold 8-byte entries):
+// seg <= B * cap / blocks. An overflowed
+// segment is not an error, it is the loud fallback (kernels_impl.h
+// emit_bin). KAKVEDA_KNN_EMIT_SEG overrides the default.
+constexpr long EMIT_SEG_DEFAULT = 8192;
+
+inline long emit_seg_cap(int B, long cap, const Chunking& ch, long env_seg) {
+  const long blocks = (long)ch.nchunks * ch.row_tiles;
+  const long budget = std::max(1L, (long)B * std::max(cap, 0L) / blocks);
+  const long want = env_seg > 0 ? env_seg : EMIT_SEG_DEFAULT;
+  return std::max(1L, std::min(want, budget));
+}
+
 enum class MainKernel { List128, Argmax128, Stash8p, Emit8p, SmallB };
 enum class MergeKernel { Small, Merge, Emit };
 
@@ -110,6 +131,7 @@ struct KnnPlan {
   int prepass_mode;      // cosine_topk_partial_t EPI_MODE the prepass runs
   bool prepass_compact;  // prepass writes its own [B][preg][KMAX] buffer
   long cap;              // emission candidates per row
+  long seg;              // emission records per block segment (Emit8p)
   int smallb_blocks;     // SmallB grid.x
   MergeKernel merge;
 };
@@ -137,6 +159,7 @@ inline KnnPlan plan_cosine_topk_filtered(int B, int N, int k, const KnnEnv& env,
               p.preg >= 8;
   p.prepass_compact = emit && p.prepass;
   p.cap = env.cap;
+  p.seg = 0;  // no 8-phase kernel carries the filter
   p.smallb_blocks = (int)std::min((long)((N + 255) / 256), 8192L);
   p.main = emit ? MainKernel::SmallB : MainKernel::List128;
   p.mode = emit ? 4 : 11;
@@ -191,6 +214,7 @@ inline KnnPlan plan_cosine_topk(int B, int N, int k, const KnnEnv& env,
               p.preg >= 8;
   p.prepass_compact = emit && p.prepass;
   p.cap = env.cap;
+  p.seg = emit && B > SMALLB_MAX ? emit_seg_cap(B, env.cap, p.ch, env.seg) : 0;
   p.smallb_blocks = (int)std::min((long)((N + 255) / 256), 8192L);
 
   if (k == 1 && !use8p) {
