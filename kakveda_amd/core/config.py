@@ -31,6 +31,13 @@ DEFAULT_CONFIG: Dict[str, Any] = {
         "top_k": 5,
         "hash_dim": 1 << 16,
         "encoder_seed": 1234,
+        # optional cluster-routed (approximate) match; exact is the default
+        "routed": {
+            "enabled": False,
+            "n_lists": None,  # None: ~sqrt(rows)
+            "nprobe": 32,
+            "min_rows": 65536,  # below this the exact scan is already cheap
+        },
     },
 }
 

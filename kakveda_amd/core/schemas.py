@@ -96,6 +96,9 @@ class FailureMatchRequest(BaseModel):
     # opt-in: apply failure_type inside the search (top-k OF that type)
     # instead of after the global top-k cut, the reference's order
     filter_first: bool = False
+    # opt out of the routed (approximate) search for this request; a no-op
+    # when the service runs exact search anyway
+    exact: bool = False
 
 
 class FailureMatch(BaseModel):

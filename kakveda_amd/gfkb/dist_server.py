@@ -161,13 +161,18 @@ class _CoordinatorStore:
     def append(self, rows: torch.Tensor) -> int:
         return self.coord.append(rows.to(self.dtype))
 
-    def search(self, queries: torch.Tensor, k: int, valid_n=None, want=None):
+    def search(self, queries: torch.Tensor, k: int, valid_n=None, want=None, nprobe=None):
         # valid_n snapshots are a single-store liveness optimisation; the
         # coordinator path is SPMD-collective and searches its live count
         if want is not None:
             raise NotImplementedError(
                 "the distributed store has no label-filtered search; "
                 "filter-first matching needs a single-store engine"
+            )
+        if nprobe:
+            raise NotImplementedError(
+                "the distributed store has no routed search; nprobe needs a "
+                "single-store engine"
             )
         return self.coord.search(queries.to(self.dtype), k)
 

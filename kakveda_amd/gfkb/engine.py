@@ -24,6 +24,7 @@ instead of whatever of that type survived the global top-k cut.
 from __future__ import annotations
 
 import json
+import logging
 import threading
 from pathlib import Path
 from typing import Any, Dict, List, Optional, Sequence, Tuple, Union
@@ -40,6 +41,11 @@ from kakveda_amd.core.schemas import (
 )
 from kakveda_amd.core.store import JsonlLog
 from kakveda_amd.encoder.model import TraceEncoder
+
+logger = logging.getLogger(__name__)
+
+#: tail rows / indexed rows past which a routed store asks for a rebuild
+STALE_WARN_FRACTION = 0.10
 
 
 class EmbeddingStore:
@@ -64,6 +70,12 @@ class EmbeddingStore:
     1536-B bf16 row), one label tensor per segment, growing and splitting
     with the rows. ``search(..., want=...)`` restricts each query to the
     rows of one label inside the scan (``ops.cosine_topk_filtered``).
+
+    Optional routed search: ``build_index()`` attaches an ``IvfIndex``
+    (gfkb/ivf.py) and ``search(..., nprobe=n)`` then scans only the n best
+    inverted lists per query plus the tail of rows appended since the build.
+    It is approximate and strictly opt-in: ``nprobe=None`` is the exact
+    search, whether an index is attached or not.
     """
 
     def __init__(
@@ -86,6 +98,9 @@ class EmbeddingStore:
         ]
         self._labels: List[torch.Tensor] = [self._new_labels(capacity)]
         self.count = 0
+        #: the routed-search index (None: exact search only)
+        self.index = None
+        self._stale_warned = False
 
     def _new_labels(self, n: int) -> torch.Tensor:
         return torch.full((n,), -1, dtype=torch.int32, device=self.device)
@@ -136,6 +151,7 @@ class EmbeddingStore:
         self._segments = [data]
         self._labels = [lab]
         self.count = n
+        self.index = None  # it described the rows just replaced
 
     def append(self, rows: torch.Tensor, labels: Optional[torch.Tensor] = None) -> int:
         """Append [n, D] rows (splitting across segments); returns the
@@ -179,12 +195,68 @@ class EmbeddingStore:
             base += seg_rows
         return out
 
+    # -- routed (IVF) search ------------------------------------------------
+
+    def build_index(self, **kw):
+        """Build an ``IvfIndex`` over the live rows and attach it (replacing
+        any earlier one). Keyword arguments go to ``IvfIndex.build``.
+        Callers that serve concurrently swap it in under their own lock
+        (``GfkbEngine.build_index``)."""
+        from kakveda_amd.gfkb.ivf import IvfIndex
+
+        index = IvfIndex.build(self, **kw)
+        self.index = index
+        self._stale_warned = False
+        return index
+
+    @property
+    def stale_fraction(self) -> float:
+        """Rows appended since the index was built, as a fraction of the
+        rows it covers (0.0 without an index). These tail rows are scanned
+        by every routed search, so the figure is the routed mode's growing
+        fixed cost, not a loss of recall."""
+        index = self.index
+        if index is None or index.n_indexed <= 0:
+            return 0.0
+        return max(self.count - index.n_indexed, 0) / float(index.n_indexed)
+
+    def _search_routed(
+        self, q: torch.Tensor, k: int, count: int, nprobe: int, index
+    ) -> Tuple[torch.Tensor, torch.Tensor]:
+        tail = self.count - index.n_indexed
+        if not self._stale_warned and tail > STALE_WARN_FRACTION * index.n_indexed:
+            self._stale_warned = True
+            logger.warning(
+                "routed index is stale: %d rows appended since it was built over "
+                "%d (%.0f%%); every routed search scans them all - rebuild with "
+                "build_index()",
+                tail,
+                index.n_indexed,
+                100.0 * tail / max(index.n_indexed, 1),
+            )
+        # a snapshot older than the index is safe: the scan drops listed ids
+        # >= count and the tail is then empty
+        return ops.ivf_search(
+            q,
+            [seg for seg, _v, _b in self._live_segments(count)],
+            index.centroids,
+            index.offsets,
+            index.ids,
+            min(nprobe, index.n_lists),
+            k,
+            count,
+            index.n_indexed,
+            index.max_list_len,
+        )
+
     def search(
         self,
         queries: torch.Tensor,
         k: int,
         valid_n: Optional[int] = None,
         want: Optional[torch.Tensor] = None,
+        nprobe: Optional[int] = None,
+        index=None,
     ) -> Tuple[torch.Tensor, torch.Tensor]:
         """Top-k over the first ``valid_n`` rows (default: the live count).
         Passing a snapshot of ``count`` makes the search safe to run
@@ -194,9 +266,29 @@ class EmbeddingStore:
         ``want`` ([B] ints) restricts query b to the rows labelled
         ``want[b]`` (negative: no restriction for that query); rows short
         of k such rows are padded with (-inf, -1). ``want=None`` is the
-        unfiltered search."""
+        unfiltered search.
+
+        ``nprobe`` > 0 asks for the routed (approximate) search over the
+        attached index: the ``nprobe`` best lists per query (clamped to the
+        list count) plus every row appended since the build. It raises
+        without an index. A label-filtered batch (``want`` set) is answered
+        by the exact filtered search whatever ``nprobe`` says: exact is
+        never worse, and a filtered query is not silently routed. ``index``
+        is the index to route through (default: the attached one), for
+        callers that snapshot it together with ``valid_n``."""
         q = queries.to(self.dtype)
         count = self.count if valid_n is None else min(int(valid_n), self.count)
+        if nprobe is not None and int(nprobe) < 0:
+            raise ValueError("nprobe must be >= 0")
+        if nprobe:
+            index = self.index if index is None else index
+            if index is None:
+                raise ValueError(
+                    "nprobe was given but the store has no routed index: "
+                    "call build_index() first"
+                )
+            if want is None and count > 0:
+                return self._search_routed(q, k, count, int(nprobe), index)
         segs = self._live_segments(count)
         w = None if want is None else want.to(device=self.device, dtype=torch.int32)
 
@@ -343,12 +435,16 @@ class GfkbEngine:
         hash_dim: int = 1 << 16,
         encoder_seed: int = 1234,
         top_k: int = 5,
+        nprobe: Optional[int] = None,
     ):
         self.data_dir = Path(data_dir)
         self.data_dir.mkdir(parents=True, exist_ok=True)
         self.failures = JsonlLog(self.data_dir / "failures.jsonl")
         self.patterns = JsonlLog(self.data_dir / "patterns.jsonl")
         self.top_k = top_k
+        #: default routed-search width of match()/match_batch(); None or 0
+        #: is the exact search. Only takes effect once an index is built.
+        self.nprobe = nprobe
         self._lock = threading.RLock()
 
         self.encoder = TraceEncoder(dim=dim, hash_dim=hash_dim, seed=encoder_seed, device=device)
@@ -421,6 +517,27 @@ class GfkbEngine:
             if self._row_identity:
                 self._restore_rows(self._row_identity)
 
+    def build_index(self, **kw):
+        """Build a routed-search index over the current rows and swap it in.
+        The build reads a snapshot of the live rows outside the lock (rows
+        below a snapshot are immutable); only the swap takes the lock. Rows
+        appended meanwhile are the new index's tail. Rebuilding is this
+        same call again."""
+        from kakveda_amd.gfkb.ivf import IvfIndex
+
+        with self._lock:
+            store = self.store
+        if not isinstance(store, EmbeddingStore):
+            raise NotImplementedError(
+                f"routed search is not supported on {type(store).__name__}"
+            )
+        index = IvfIndex.build(store, **kw)
+        with self._lock:
+            if self.store is store:
+                store.index = index
+                store._stale_warned = False
+        return index
+
     # -- failures ----------------------------------------------------------
 
     def list_failures(self) -> List[Dict[str, Any]]:
@@ -488,16 +605,19 @@ class GfkbEngine:
         failure_type: Optional[str] = None,
         top_k: Optional[int] = None,
         filter_first: bool = False,
+        nprobe: Optional[int] = None,
     ) -> List[FailureMatch]:
         """Top-k failures by cosine similarity, then optional type filter
         (reference order: cut to top-k first, filter second). With
         ``filter_first`` the type filter runs inside the search instead:
-        the top-k of the failures of that type."""
+        the top-k of the failures of that type. ``nprobe``: see
+        ``match_batch``."""
         return self.match_batch(
             [signature_text],
             failure_types=[failure_type],
             top_k=top_k,
             filter_first=filter_first,
+            nprobe=nprobe,
         )[0]
 
     def match_batch(
@@ -506,6 +626,7 @@ class GfkbEngine:
         failure_types: Optional[List[Optional[str]]] = None,
         top_k: Optional[int] = None,
         filter_first: Union[bool, Sequence[bool]] = False,
+        nprobe: Optional[int] = None,
     ) -> List[List[FailureMatch]]:
         """Match a whole batch of signatures with ONE fused-kernel launch.
 
@@ -523,6 +644,14 @@ class GfkbEngine:
         global top-k. Queries without it keep the reference's post-filter
         order; a batch may mix both, and a batch with none set takes the
         unfiltered kernels. A type no failure has ever had matches nothing.
+
+        ``nprobe`` (one value per batch; default: the engine's) > 0 routes
+        the batch through the store's index: approximate, scanning that
+        many inverted lists per query plus the rows appended since the
+        build. 0 forces the exact search. Without an index the engine's
+        default is ignored (an explicit ``nprobe`` raises); a batch with a
+        filter-first query runs the exact filtered search; sharded and
+        distributed stores refuse an explicit ``nprobe``.
         """
         nq = len(signature_texts)
         k = top_k or self.top_k
@@ -536,6 +665,7 @@ class GfkbEngine:
         with self._lock:
             store = self.store
             valid = store.count
+            index = getattr(store, "index", None)
             # per query: want = the label id to search under (None: no
             # filter in the search); unknown = filter-first on a type the
             # vocabulary has never seen
@@ -557,6 +687,16 @@ class GfkbEngine:
                 "sharded and distributed stores keep no row labels, and "
                 "post-filtering instead would silently change the result"
             )
+        if nprobe and not isinstance(store, EmbeddingStore):
+            raise NotImplementedError(
+                f"nprobe is not supported on {type(store).__name__}: sharded "
+                "and distributed stores have no routed index"
+            )
+        if nprobe is None:
+            # the engine default applies only where it can
+            probe = self.nprobe if index is not None else None
+        else:
+            probe = nprobe
         # unknown types cannot match: search only the other queries
         live = [r for r in range(nq) if not unknown[r]]
         if not live:
@@ -567,6 +707,10 @@ class GfkbEngine:
                 [-1 if want[r] is None else want[r] for r in live], dtype=torch.int32
             )
             scores, idx = store.search(q, min(k, valid), valid_n=valid, want=want_t)
+        elif probe:
+            scores, idx = store.search(
+                q, min(k, valid), valid_n=valid, nprobe=probe, index=index
+            )
         else:
             scores, idx = store.search(q, min(k, valid), valid_n=valid)
         slot = {r: j for j, r in enumerate(live)}

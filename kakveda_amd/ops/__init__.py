@@ -15,6 +15,10 @@ Kernels (kakveda_amd/ops/hip/):
 - kmeans_assign / kmeans_update — streaming k-means for the pattern
   detector (assignment reuses the score GEMM; update is a segmented
   reduction).
+- ivf_route_scores / ivf_scan_topk / ivf_search — the optional cluster-routed
+  (IVF) search: centroid scoring, then a gather scan of the probed inverted
+  lists plus the rows appended since the index was built (approximate; the
+  exact search stays the default).
 
 Policy: on a CUDA(ROCm) device the HIP extension is REQUIRED — ops raise
 if it is missing rather than silently falling back to eager PyTorch. The
@@ -281,3 +285,190 @@ def kmeans_update(
     counts = torch.zeros(n_clusters, dtype=torch.float32, device=points.device)
     counts.index_add_(0, assign.long(), torch.ones_like(assign, dtype=torch.float32))
     return sums, counts
+
+
+# ---------------------------------------------------------------------------
+# cluster-routed (IVF) search
+# ---------------------------------------------------------------------------
+
+def _pad_topk(scores: torch.Tensor, idx: torch.Tensor, k: int):
+    kk = scores.shape[1]
+    if kk >= k:
+        return scores, idx
+    B = scores.shape[0]
+    pad_s = torch.full((B, k - kk), float("-inf"), dtype=scores.dtype, device=scores.device)
+    pad_i = torch.full((B, k - kk), -1, dtype=idx.dtype, device=idx.device)
+    return torch.cat([scores, pad_s], dim=1), torch.cat([idx, pad_i], dim=1)
+
+
+def _segment_list(segments) -> list:
+    return [segments] if isinstance(segments, torch.Tensor) else list(segments)
+
+
+def _gather_rows(segments: list, rows: torch.Tensor) -> torch.Tensor:
+    """Rows (global ids, int64) of a segmented store as one [n, D] tensor."""
+    if len(segments) == 1:
+        return segments[0][rows]
+    out = torch.empty(rows.shape[0], segments[0].shape[1], dtype=segments[0].dtype,
+                      device=segments[0].device)
+    base = 0
+    for seg in segments:
+        n = int(seg.shape[0])
+        m = (rows >= base) & (rows < base + n)
+        if bool(m.any()):
+            out[m] = seg[rows[m] - base]
+        base += n
+    return out
+
+
+def ivf_route_scores(queries: torch.Tensor, centroids: torch.Tensor) -> torch.Tensor:
+    """Dense fp32 scores [B, L] of the queries against the IVF centroids."""
+    if queries.device.type == "cuda":
+        return _require_ext().ivf_route_scores(queries, centroids)
+    return queries.float() @ centroids.float().t()
+
+
+def ivf_scan_topk_ref(
+    queries: torch.Tensor,
+    segments,
+    offsets: torch.Tensor,
+    ids: torch.Tensor,
+    probes: torch.Tensor,
+    k: int,
+    valid_n: int,
+    tail_lo: int,
+    tail_hi: int,
+) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Plain-PyTorch reference of ``ivf_scan_topk`` (fp32 accumulate)."""
+    segs = _segment_list(segments)
+    dev = queries.device
+    B = queries.shape[0]
+    L = int(offsets.shape[0]) - 1
+    off = offsets.to("cpu").long().tolist()
+    ids_l = ids.to(dev).long()
+    tail = torch.arange(int(tail_lo), int(tail_hi), dtype=torch.int64, device=dev)
+    out_s = torch.full((B, k), float("-inf"), dtype=torch.float32, device=dev)
+    out_i = torch.full((B, k), -1, dtype=torch.int64, device=dev)
+    for b, row in enumerate(probes.to("cpu").long().tolist()):
+        parts = [ids_l[off[l] : off[l + 1]] for l in row if 0 <= l < L]
+        rows = torch.cat(parts + [tail])
+        rows = rows[(rows >= 0) & (rows < int(valid_n))]
+        if rows.numel() == 0:
+            continue
+        sims = _gather_rows(segs, rows).float() @ queries[b].float()
+        kk = min(k, int(rows.numel()))
+        s, sel = torch.topk(sims, kk)
+        out_s[b, :kk] = s
+        out_i[b, :kk] = rows[sel]
+    return out_s, out_i
+
+
+def ivf_scan_topk(
+    queries: torch.Tensor,
+    segments,
+    offsets: torch.Tensor,
+    ids: torch.Tensor,
+    probes: torch.Tensor,
+    k: int,
+    valid_n: int,
+    tail_lo: int,
+    tail_hi: int,
+    max_list_len: int = 0,
+) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Exact top-k of each query over a candidate set given as inverted lists.
+
+    segments: the store's row tensors in order ([n_i, D]; one tensor is
+    accepted too); ``ids`` int32 holds global row ids, list l being
+    ``ids[offsets[l]:offsets[l+1]]``; ``probes`` int32 [B, nprobe] names the
+    lists each query scans (entries outside [0, L) are skipped, so -1 pads;
+    the others must be distinct per query). Every query also scans the
+    contiguous rows [tail_lo, tail_hi). Row ids outside [0, valid_n) are
+    ignored. Returns (scores f32 [B, k], idx i64 [B, k]) sorted descending,
+    padded with (-inf, -1) where the candidate set is shorter than k and
+    past KMAX columns on GPU. ``max_list_len`` (the longest list, if known)
+    only sizes the GPU grid.
+    """
+    if queries.device.type != "cuda":
+        return ivf_scan_topk_ref(
+            queries, segments, offsets, ids, probes, k, valid_n, tail_lo, tail_hi
+        )
+    ext = _require_ext()
+    dev = queries.device
+    kk = min(int(k), KMAX)
+    scores, idx = ext.ivf_scan_topk(
+        queries,
+        _segment_list(segments),
+        offsets.to(device=dev, dtype=torch.int64).contiguous(),
+        ids.to(device=dev, dtype=torch.int32).contiguous(),
+        probes.to(device=dev, dtype=torch.int32).contiguous(),
+        kk,
+        int(valid_n),
+        int(tail_lo),
+        int(tail_hi),
+        int(max_list_len),
+    )
+    scores = torch.where(idx < 0, torch.full_like(scores, float("-inf")), scores)
+    return _pad_topk(scores, idx, k)
+
+
+def ivf_search_ref(
+    queries: torch.Tensor,
+    segments,
+    centroids: torch.Tensor,
+    offsets: torch.Tensor,
+    ids: torch.Tensor,
+    nprobe: int,
+    k: int,
+    valid_n: int,
+    n_indexed: int,
+) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Plain-PyTorch reference of ``ivf_search`` (fp32 accumulate)."""
+    route = queries.float() @ centroids.float().t()
+    probes = torch.topk(route, min(int(nprobe), route.shape[1]), dim=1).indices
+    return ivf_scan_topk_ref(
+        queries, segments, offsets, ids, probes, k, valid_n,
+        min(int(n_indexed), int(valid_n)), valid_n,
+    )
+
+
+def ivf_search(
+    queries: torch.Tensor,
+    segments,
+    centroids: torch.Tensor,
+    offsets: torch.Tensor,
+    ids: torch.Tensor,
+    nprobe: int,
+    k: int,
+    valid_n: int,
+    n_indexed: int,
+    max_list_len: int = 0,
+) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Cluster-routed approximate top-k: score the L centroids, scan the
+    ``nprobe`` best lists of each query plus the tail [n_indexed, valid_n)
+    of rows appended since the index was built, return the exact top-k of
+    that candidate set. With ``nprobe == L`` the candidate set is every row
+    and the result is the exact search's. Shapes and padding as
+    ``ivf_scan_topk``."""
+    L = int(centroids.shape[0])
+    nprobe = max(1, min(int(nprobe), L))
+    if queries.device.type != "cuda":
+        return ivf_search_ref(
+            queries, segments, centroids, offsets, ids, nprobe, k, valid_n, n_indexed
+        )
+    ext = _require_ext()
+    dev = queries.device
+    kk = min(int(k), KMAX)
+    scores, idx = ext.ivf_search(
+        queries,
+        _segment_list(segments),
+        centroids,
+        offsets.to(device=dev, dtype=torch.int64).contiguous(),
+        ids.to(device=dev, dtype=torch.int32).contiguous(),
+        nprobe,
+        kk,
+        int(valid_n),
+        int(n_indexed),
+        int(max_list_len),
+    )
+    scores = torch.where(idx < 0, torch.full_like(scores, float("-inf")), scores)
+    return _pad_topk(scores, idx, k)

@@ -1,0 +1,246 @@
+// Cluster-routed (IVF) search kernels: centroid scoring and the scan of the
+// probed inverted lists. Included by kakveda_kernels.hip after
+// kernels_impl.h (bf16x8 / f32x4 / enc_f32 / NEG_INF come from there).
+//
+// The store's rows stay where they are: a list is a run of row ids in the
+// CSR `ids` array and the scan gathers whole rows through it (1,536-B rows
+// at D=768; whole-row register gathers of that size read close to the
+// streaming rate on CDNA4). Nothing here shares a body with the exact
+// kernels, so their machine code does not move.
+#pragma once
+
+#include <hip/hip_runtime.h>
+#include "ivf_plan.h"
+
+namespace kakveda {
+
+// The store's segments, passed by value: row r lives in segment
+// ivf_segment_of(r, s0, q) at local row ivf_local_row(r, s0, q).
+struct IvfSegs {
+  const bf16_t* base[IVF_MAX_SEGMENTS];
+  long s0;  // rows of the first segment
+  long q;   // rows of every later segment (1 when there is none)
+};
+
+// ---------------------------------------------------------------------------
+// ivf_route_scores: dense fp32 scores [B][L] of the queries against the
+// bf16 centroids. grid = (ceil(L/32), ceil(B/8)), 256 threads; a block holds
+// its <= 8 queries in LDS and streams 32 centroid rows per iteration, 8
+// lanes per row (the smallb v4 mapping), then stores every score: plain
+// stores, no atomics, no thresholds.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void ivf_route_scores(
+    const bf16_t* __restrict__ Q, const bf16_t* __restrict__ C,
+    float* __restrict__ out, int B, int L, int D) {
+  extern __shared__ char ivf_qmem[];  // [nb][D] bf16 queries
+  const int b0 = blockIdx.y * 8;
+  const int nb = B - b0 < 8 ? B - b0 : 8;
+  const bf16x8* qsrc = (const bf16x8*)(Q + (size_t)b0 * D);
+  for (int i = threadIdx.x; i < nb * (D / 8); i += 256)
+    ((bf16x8*)ivf_qmem)[i] = qsrc[i];
+  __syncthreads();
+
+  const int lane = threadIdx.x & 63;
+  const int wid = threadIdx.x >> 6;
+  const int rr = lane >> 3;
+  const int ch = lane & 7;
+  const int nseg = D / 64;
+  for (int r0 = blockIdx.x * 32 + wid * 8; r0 < L; r0 += gridDim.x * 32) {
+    const int r = r0 + rr < L ? r0 + rr : L - 1;  // clamp tail loads
+    const bf16x8* row = (const bf16x8*)(C + (size_t)r * D);
+    f32x4 accv[8];
+#pragma unroll
+    for (int b = 0; b < 8; ++b) accv[b] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int j = 0; j < nseg; ++j) {
+      const bf16x8 cv = row[j * 8 + ch];
+#pragma unroll
+      for (int b = 0; b < 8; ++b) {
+        if (b < nb) {
+          const bf16x8 qv =
+              ((const bf16x8*)(ivf_qmem + (size_t)b * D * 2))[j * 8 + ch];
+#pragma unroll
+          for (int e = 0; e < 8; ++e)
+            accv[b][e & 3] += (float)cv[e] * (float)qv[e];
+        }
+      }
+    }
+#pragma unroll
+    for (int b = 0; b < 8; ++b) {
+      if (b < nb) {
+        float s = (accv[b][0] + accv[b][1]) + (accv[b][2] + accv[b][3]);
+        s += __shfl_xor(s, 1, 64);
+        s += __shfl_xor(s, 2, 64);
+        s += __shfl_xor(s, 4, 64);
+        if (ch == 0 && r0 + rr < L) out[(size_t)(b0 + b) * L + r0 + rr] = s;
+      }
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------
+// ivf_scan_topk_kernel: the routed scan. grid = (slices, nprobe + 1, B),
+// 256 threads, D*2 bytes of dynamic LDS (the block's one query).
+//
+// blockIdx.y < nprobe: the list probes[b][y] (rows ids[offsets[l] ..
+// offsets[l+1])); blockIdx.y == nprobe: the contiguous tail [tail_lo,
+// tail_hi), the rows appended since the index was built. A block walks its
+// source from position blockIdx.x*32 in strides of slices*32, each wave 8
+// rows x 8 lanes, so a long list is split over `slices` blocks instead of
+// being one wave's whole load.
+//
+// Every row group keeps a sorted top-KMAX of packed (score bits << 32) |
+// (0x7fffffff - row) candidates in registers (its 8 lanes hold the same
+// list); one LDS tree merge over the block's 32 groups leaves the block's
+// top-KMAX, stored to the block's own slot cand[b][(y*slices + x)*KMAX ..]
+// with 0 for "empty". No atomics and no floors: every block writes exactly
+// its KMAX entries, and emit_merge_topk (whose empty sentinel is 0) finishes
+// over the preset count.
+//
+// Guards: a probe outside [0, L) is an empty source; list bounds are clamped
+// to [0, n_ids]; a row id outside [0, valid_n) is scored from row 0 and never
+// inserted (so a snapshot valid_n below some listed ids is safe); positions
+// past the end of the source load the source's last position and are not
+// inserted. valid_n >= 1 and every row below valid_n lies in a segment the
+// host has checked.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void ivf_scan_topk_kernel(
+    const bf16_t* __restrict__ Q, const IvfSegs segs,
+    const long* __restrict__ offsets, const int* __restrict__ ids,
+    const int* __restrict__ probes, int nprobe, int L, long n_ids, int D,
+    long valid_n, long tail_lo, long tail_hi,
+    unsigned long long* __restrict__ cand) {
+  extern __shared__ char ivf_qmem[];  // [D] bf16: this block's query
+  __shared__ unsigned long long all[32 * KMAX];
+  const int b = blockIdx.z;
+  const int y = blockIdx.y;
+  const int tid = threadIdx.x;
+  const bool is_tail = y == nprobe;
+
+  long lo = 0, len = 0;
+  if (is_tail) {
+    lo = tail_lo;
+    len = tail_hi - tail_lo;
+  } else {
+    const int l = probes[(size_t)b * nprobe + y];
+    if (l >= 0 && l < L) {
+      lo = offsets[l];
+      long hi = offsets[l + 1];
+      lo = lo < 0 ? 0 : lo;
+      hi = hi > n_ids ? n_ids : hi;
+      len = hi - lo;
+    }
+  }
+  unsigned long long* slot =
+      cand + ((size_t)b * gridDim.y * gridDim.x +
+              (size_t)y * gridDim.x + blockIdx.x) * KMAX;
+  if ((long)blockIdx.x * 32 >= len) {  // nothing in this slice (block-uniform)
+    if (tid < KMAX) slot[tid] = 0ull;
+    return;
+  }
+
+  const bf16x8* qsrc = (const bf16x8*)(Q + (size_t)b * D);
+  for (int i = tid; i < D / 8; i += 256) ((bf16x8*)ivf_qmem)[i] = qsrc[i];
+  __syncthreads();
+
+  const int lane = tid & 63;
+  const int wid = tid >> 6;
+  const int rr = lane >> 3;  // row within this wave's 8
+  const int ch = lane & 7;   // 16-byte chunk within a 128-B segment
+  const int nseg = D / 64;
+  const bf16x8* qv8 = (const bf16x8*)ivf_qmem;
+
+  unsigned long long loc[KMAX];  // sorted desc; 0 = empty
+#pragma unroll
+  for (int q = 0; q < KMAX; ++q) loc[q] = 0ull;
+
+  for (long p0 = (long)blockIdx.x * 32 + wid * 8; p0 < len;
+       p0 += (long)gridDim.x * 32) {
+    const long p = p0 + rr;
+    const long pc = p < len ? p : len - 1;  // clamp tail loads
+    const long r = is_tail ? lo + pc : (long)ids[lo + pc];
+    const bool ok = p < len && r >= 0 && r < valid_n;
+    const long rc = ok ? r : 0;
+    const int si = ivf_segment_of(rc, segs.s0, segs.q);
+    const bf16x8* row =
+        (const bf16x8*)(segs.base[si] + ivf_local_row(rc, segs.s0, segs.q) * D);
+    f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
+    f32x4 acc2 = f32x4{0.f, 0.f, 0.f, 0.f};
+    int j = 0;
+    for (; j + 4 <= nseg; j += 4) {
+      bf16x8 cv[4];
+#pragma unroll
+      for (int v = 0; v < 4; ++v) cv[v] = row[(j + v) * 8 + ch];
+#pragma unroll
+      for (int v = 0; v < 4; ++v) {
+        const bf16x8 qv = qv8[(j + v) * 8 + ch];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          acc[e] += (float)cv[v][e] * (float)qv[e];
+          acc2[e] += (float)cv[v][e + 4] * (float)qv[e + 4];
+        }
+      }
+    }
+    for (; j < nseg; ++j) {  // D % 256 != 0 tail segments
+      const bf16x8 cv = row[j * 8 + ch];
+      const bf16x8 qv = qv8[j * 8 + ch];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        acc[e] += (float)cv[e] * (float)qv[e];
+        acc2[e] += (float)cv[e + 4] * (float)qv[e + 4];
+      }
+    }
+    float s = ((acc[0] + acc[1]) + (acc[2] + acc[3])) +
+              ((acc2[0] + acc2[1]) + (acc2[2] + acc2[3]));
+    s += __shfl_xor(s, 1, 64);
+    s += __shfl_xor(s, 2, 64);
+    s += __shfl_xor(s, 4, 64);  // the row group's 8 lanes now agree
+    const unsigned long long v =
+        ok ? ((unsigned long long)enc_f32(s) << 32) |
+                 (unsigned)(0x7fffffff - (int)r)
+           : 0ull;
+    if (v > loc[KMAX - 1]) {
+      loc[KMAX - 1] = v;  // insert at tail, bubble up (array stays sorted)
+#pragma unroll
+      for (int q = KMAX - 1; q > 0; --q)
+        if (loc[q] > loc[q - 1]) {
+          const unsigned long long t = loc[q];
+          loc[q] = loc[q - 1];
+          loc[q - 1] = t;
+        }
+    }
+  }
+
+  const int grp = tid >> 3;  // 32 row groups per block
+  if (ch == 0) {
+#pragma unroll
+    for (int q = 0; q < KMAX; ++q) all[grp * KMAX + q] = loc[q];
+  }
+  __syncthreads();
+  for (int stride = 16; stride >= 1; stride >>= 1) {
+    if (tid < stride) {
+      // two-pointer merge of two sorted-desc KMAX lists -> top KMAX
+      // (LDS-indexed, as in emit_merge_topk)
+      const unsigned long long* pa = all + (size_t)tid * KMAX;
+      const unsigned long long* pb = all + (size_t)(tid + stride) * KMAX;
+      unsigned long long o[KMAX];
+      int ia = 0, ib = 0;
+#pragma unroll
+      for (int q = 0; q < KMAX; ++q) {
+        const unsigned long long va = pa[ia], vb = pb[ib];
+        if (va >= vb) {
+          o[q] = va;
+          ++ia;
+        } else {
+          o[q] = vb;
+          ++ib;
+        }
+      }
+#pragma unroll
+      for (int q = 0; q < KMAX; ++q) all[tid * KMAX + q] = o[q];
+    }
+    __syncthreads();
+  }
+  if (tid < KMAX) slot[tid] = all[tid];
+}
+
+}  // namespace kakveda

@@ -4,7 +4,9 @@
 #include <c10/hip/HIPStream.h>
 #include <cstdlib>
 #include <string>
+#include <vector>
 #include "kernels_impl.h"
+#include "ivf_impl.h"
 
 using namespace kakveda;
 
@@ -539,6 +541,161 @@ double probe8p(torch::Tensor queries, torch::Tensor corpus, int64_t mode,
   return (double)ms / (double)iters;
 }
 
+// ---- cluster-routed (IVF) search ------------------------------------------
+
+namespace {
+
+void check_i32_gpu(const torch::Tensor& t, int64_t dim, const char* name) {
+  TORCH_CHECK(t.is_cuda() && t.scalar_type() == torch::kInt32 &&
+                  t.dim() == dim && t.is_contiguous(),
+              name, " must be contiguous ", dim, "-D i32 on GPU");
+}
+
+// The by-value segment table of a routed launch; refuses, before anything
+// is launched, a store the kernel's row -> segment function cannot address.
+IvfSegs ivf_segs(const std::vector<torch::Tensor>& segments,
+                 const torch::Tensor& queries, long valid_n) {
+  const int n = (int)segments.size();
+  long q = 1;
+  try {
+    q = ivf_check_segments(n, [&](int i) { return (long)segments[i].size(0); });
+  } catch (const std::invalid_argument& e) {
+    TORCH_CHECK(false, e.what());
+  }
+  IvfSegs s{};
+  long total = 0;
+  for (int i = 0; i < n; ++i) {
+    check_bf16_2d(segments[i], "segment");
+    TORCH_CHECK(segments[i].device() == queries.device(),
+                "segments and queries must be on one device");
+    TORCH_CHECK(segments[i].size(1) == queries.size(1), "dim mismatch");
+    s.base[i] = (const bf16_t*)segments[i].data_ptr();
+    total += segments[i].size(0);
+  }
+  for (int i = n; i < IVF_MAX_SEGMENTS; ++i) s.base[i] = s.base[0];
+  s.s0 = segments[0].size(0);
+  s.q = q;
+  TORCH_CHECK(valid_n >= 1 && valid_n <= total && valid_n <= 0x7fffffffL,
+              "valid_n out of range");
+  return s;
+}
+
+}  // namespace
+
+torch::Tensor ivf_route_scores_op(torch::Tensor queries, torch::Tensor centroids) {
+  check_bf16_2d(queries, "queries");
+  check_bf16_2d(centroids, "centroids");
+  const int B = queries.size(0), D = queries.size(1), L = centroids.size(0);
+  TORCH_CHECK(centroids.device() == queries.device(),
+              "centroids and queries must be on one device");
+  TORCH_CHECK(centroids.size(1) == D, "dim mismatch");
+  TORCH_CHECK(D % 64 == 0 && D >= 64, "D must be a multiple of 64");
+  TORCH_CHECK((size_t)8 * D * 2 <= 64 * 1024, "D too large for LDS queries");
+  TORCH_CHECK(B >= 1 && L >= 1, "empty queries or centroids");
+  TORCH_CHECK((B + 7) / 8 <= 65535, "too many queries for one launch");
+  auto out = torch::empty(
+      {B, L}, torch::TensorOptions().dtype(torch::kFloat32).device(queries.device()));
+  const int gx = std::min((L + 31) / 32, 4096);
+  hipLaunchKernelGGL(ivf_route_scores, dim3(gx, (B + 7) / 8), dim3(256),
+                     (size_t)std::min(B, 8) * D * 2,
+                     c10::hip::getCurrentHIPStream().stream(),
+                     (const bf16_t*)queries.data_ptr(),
+                     (const bf16_t*)centroids.data_ptr(), out.data_ptr<float>(),
+                     B, L, D);
+  return out;
+}
+
+std::tuple<torch::Tensor, torch::Tensor> ivf_scan_topk(
+    torch::Tensor queries, std::vector<torch::Tensor> segments,
+    torch::Tensor offsets, torch::Tensor ids, torch::Tensor probes, int64_t k,
+    int64_t valid_n, int64_t tail_lo, int64_t tail_hi, int64_t max_list_len) {
+  // Exact top-k of each query over the rows of its probed lists plus the
+  // tail [tail_lo, tail_hi). max_list_len only sizes the grid (any value
+  // >= 0 gives the same result); rows short of k candidates come back padded
+  // with (NEG_INF, -1), which the Python op normalises.
+  check_bf16_2d(queries, "queries");
+  const int B = queries.size(0), D = queries.size(1);
+  const IvfSegs segs = ivf_segs(segments, queries, (long)valid_n);
+  TORCH_CHECK(D % 64 == 0 && D >= 64, "D must be a multiple of 64");
+  TORCH_CHECK((size_t)D * 2 <= 64 * 1024, "D too large for an LDS query");
+  TORCH_CHECK(k >= 1 && k <= KMAX, "k must be in [1,", KMAX, "]");
+  TORCH_CHECK(B >= 1, "no queries");
+  TORCH_CHECK(offsets.is_cuda() && offsets.scalar_type() == torch::kInt64 &&
+                  offsets.dim() == 1 && offsets.is_contiguous() &&
+                  offsets.size(0) >= 1,
+              "offsets must be contiguous 1-D i64 on GPU with L+1 entries");
+  check_i32_gpu(ids, 1, "ids");
+  check_i32_gpu(probes, 2, "probes");
+  TORCH_CHECK(offsets.device() == queries.device() &&
+                  ids.device() == queries.device() &&
+                  probes.device() == queries.device(),
+              "offsets, ids, probes and queries must be on one device");
+  TORCH_CHECK(probes.size(0) == B, "probes needs one row per query");
+  const int L = (int)offsets.size(0) - 1;
+  const int nprobe = (int)probes.size(1);
+  TORCH_CHECK(nprobe <= 65534, "nprobe too large");
+  TORCH_CHECK(tail_lo >= 0 && tail_lo <= tail_hi && tail_hi <= valid_n,
+              "tail range must satisfy 0 <= tail_lo <= tail_hi <= valid_n");
+  TORCH_CHECK(max_list_len >= 0, "max_list_len must be >= 0");
+
+  auto dev = queries.device();
+  auto stream = c10::hip::getCurrentHIPStream().stream();
+  auto out_score = torch::empty(
+      {B, k}, torch::TensorOptions().dtype(torch::kFloat32).device(dev));
+  auto out_idx =
+      torch::empty({B, k}, torch::TensorOptions().dtype(torch::kInt64).device(dev));
+  const IvfPlan p =
+      plan_ivf_scan((long)max_list_len, (long)(tail_hi - tail_lo), nprobe, B);
+  // grid.z holds at most IVF_MAX_GRID_Z queries: chunk the batch
+  for (int b0 = 0; b0 < B; b0 += IVF_MAX_GRID_Z) {
+    const int nb = std::min(B - b0, IVF_MAX_GRID_Z);
+    auto cand = torch::empty(
+        {(long)nb, p.cand_entries},
+        torch::TensorOptions().dtype(torch::kInt64).device(dev));
+    auto ccount = torch::full(
+        {(long)nb}, (int64_t)p.cand_entries,
+        torch::TensorOptions().dtype(torch::kInt32).device(dev));
+    hipLaunchKernelGGL(
+        ivf_scan_topk_kernel, dim3(p.slices, p.sources, nb), dim3(256),
+        (size_t)D * 2, stream, (const bf16_t*)queries.data_ptr() + (size_t)b0 * D,
+        segs, (const long*)offsets.data_ptr<int64_t>(), ids.data_ptr<int>(),
+        probes.data_ptr<int>() + (size_t)b0 * nprobe, nprobe, L,
+        (long)ids.size(0), D, (long)valid_n, (long)tail_lo, (long)tail_hi,
+        (unsigned long long*)cand.data_ptr<int64_t>());
+    hipLaunchKernelGGL(emit_merge_topk, dim3(nb), dim3(256), 0, stream,
+                       (const unsigned long long*)cand.data_ptr<int64_t>(),
+                       (const unsigned*)ccount.data_ptr<int>(),
+                       out_score.data_ptr<float>() + (size_t)b0 * k,
+                       (long*)out_idx.data_ptr<int64_t>() + (size_t)b0 * k, nb,
+                       p.cand_entries, (int)k);
+  }
+  return {out_score, out_idx};
+}
+
+std::tuple<torch::Tensor, torch::Tensor> ivf_search(
+    torch::Tensor queries, std::vector<torch::Tensor> segments,
+    torch::Tensor centroids, torch::Tensor offsets, torch::Tensor ids,
+    int64_t nprobe, int64_t k, int64_t valid_n, int64_t n_indexed,
+    int64_t max_list_len) {
+  // route -> select -> scan: score the centroids, take the nprobe best
+  // lists per query (torch.topk on the tiny [B, L] score tensor), scan
+  // those lists plus the tail [n_indexed, valid_n) (empty when valid_n is
+  // a snapshot from before the index was built; listed ids >= valid_n are
+  // dropped by the scan).
+  TORCH_CHECK(offsets.dim() == 1 && offsets.size(0) == centroids.size(0) + 1,
+              "offsets must have L+1 entries for L centroids");
+  TORCH_CHECK(ids.dim() == 1 && ids.size(0) == n_indexed,
+              "ids must have n_indexed entries");
+  TORCH_CHECK(n_indexed >= 0, "n_indexed must be >= 0");
+  const int64_t L = centroids.size(0);
+  TORCH_CHECK(nprobe >= 1 && nprobe <= L, "nprobe must be in [1, n_lists]");
+  auto scores = ivf_route_scores_op(queries, centroids);
+  auto probes = std::get<1>(scores.topk(nprobe, 1)).to(torch::kInt32).contiguous();
+  return ivf_scan_topk(queries, std::move(segments), offsets, ids, probes, k,
+                       valid_n, std::min(n_indexed, valid_n), valid_n,
+                       max_list_len);
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("cosine_topk", &cosine_topk, "fused cosine top-k (MFMA + LDS top-k)");
   m.def("cosine_topk_filtered", &cosine_topk_filtered,
@@ -556,5 +713,19 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "emission per-row count debug probe", pybind11::arg("queries"),
         pybind11::arg("corpus"), pybind11::arg("pregq"),
         pybind11::arg("k") = (int64_t)KMAX);
+  m.def("ivf_route_scores", &ivf_route_scores_op,
+        "dense fp32 scores of queries against IVF centroids");
+  m.def("ivf_scan_topk", &ivf_scan_topk,
+        "exact top-k over probed inverted lists plus a contiguous tail",
+        pybind11::arg("queries"), pybind11::arg("segments"),
+        pybind11::arg("offsets"), pybind11::arg("ids"), pybind11::arg("probes"),
+        pybind11::arg("k"), pybind11::arg("valid_n"), pybind11::arg("tail_lo"),
+        pybind11::arg("tail_hi"), pybind11::arg("max_list_len") = (int64_t)0);
+  m.def("ivf_search", &ivf_search, "cluster-routed (IVF) top-k search",
+        pybind11::arg("queries"), pybind11::arg("segments"),
+        pybind11::arg("centroids"), pybind11::arg("offsets"),
+        pybind11::arg("ids"), pybind11::arg("nprobe"), pybind11::arg("k"),
+        pybind11::arg("valid_n"), pybind11::arg("n_indexed"),
+        pybind11::arg("max_list_len") = (int64_t)0);
   m.attr("KMAX") = KMAX;
 }

@@ -76,7 +76,11 @@ class ShardedStore:
         return torch.where(local_idx < 0, local_idx, out)
 
     def search(
-        self, queries: torch.Tensor, k: int, want: Optional[torch.Tensor] = None
+        self,
+        queries: torch.Tensor,
+        k: int,
+        want: Optional[torch.Tensor] = None,
+        nprobe: Optional[int] = None,
     ) -> Tuple[torch.Tensor, torch.Tensor]:
         """Global top-k: local fused search + all-gather + merge.
 
@@ -84,8 +88,14 @@ class ShardedStore:
         ranks, equal to a single-store search over the same data.
 
         Label-filtered search (``want``) is a single-store feature so far:
-        shards carry no row labels, so asking for it raises.
+        shards carry no row labels, so asking for it raises. So does
+        routed search (``nprobe``): shards keep no routed index.
         """
+        if nprobe:
+            raise NotImplementedError(
+                "ShardedStore has no routed search (shards keep no routed "
+                "index); nprobe needs a single-store engine"
+            )
         if want is not None:
             raise NotImplementedError(
                 "ShardedStore has no label-filtered search (shards keep no "

@@ -45,7 +45,7 @@ class LocalCluster:
 
         self.engine = engine or GfkbEngine(data_dir=data_dir, device=device)
         self.event_bus = event_bus_mod.create_app(transport=self.tx)
-        self.gfkb = gfkb_mod.create_app(engine=self.engine)
+        self.gfkb = gfkb_mod.create_app(engine=self.engine, config=cfg)
         self.ingestion = ing_mod.create_app(event_bus_url=u["event_bus"], transport=self.tx)
         self.failure_classifier = fc_mod.create_app(
             event_bus_url=u["event_bus"],

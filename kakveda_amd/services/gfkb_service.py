@@ -9,6 +9,7 @@ instead of a per-request TF-IDF refit.
 
 from __future__ import annotations
 
+import logging
 import os
 import queue
 import threading
@@ -23,6 +24,8 @@ from kakveda_amd.core.schemas import (
     Severity,
 )
 from kakveda_amd.gfkb.engine import GfkbEngine
+
+logger = logging.getLogger(__name__)
 
 
 class MatchBatcher:
@@ -60,12 +63,14 @@ class MatchBatcher:
         signature_text: str,
         failure_type: Optional[str] = None,
         filter_first: bool = False,
+        exact: bool = False,
     ):
         self._ensure_thread()
         item: Dict[str, Any] = {
             "text": signature_text,
             "ftype": failure_type,
             "first": filter_first,
+            "exact": exact,
             "ev": threading.Event(),
             "res": None,
             "err": None,
@@ -89,6 +94,9 @@ class MatchBatcher:
                 first = [b["first"] for b in batch]
                 # an all-unset batch makes the call it always made
                 extra = {"filter_first": first} if any(first) else {}
+                # one request asking for exact makes its whole batch exact
+                if any(b["exact"] for b in batch):
+                    extra["nprobe"] = 0
                 results = self.engine.match_batch(
                     [b["text"] for b in batch], [b["ftype"] for b in batch], **extra
                 )
@@ -120,11 +128,40 @@ class UpsertPatternRequest(BaseModel):
     description: Optional[str] = None
 
 
+def _setup_routed(engine: GfkbEngine, config: Optional[Any]) -> None:
+    """Apply the ``gfkb.routed`` config block: when enabled, build the routed
+    index at start-up if the store is big enough and make its ``nprobe`` the
+    engine default. Disabled (the default) touches nothing."""
+    if config is None:
+        from kakveda_amd.core.config import ConfigStore
+
+        config = ConfigStore()
+    routed = config.get("gfkb.routed", {}) or {}
+    if not routed.get("enabled", False):
+        return
+    rows = engine.store.count
+    min_rows = int(routed.get("min_rows", 65536) or 0)
+    if rows < max(min_rows, 1):
+        logger.info(
+            "routed search enabled but the store has %d rows (< min_rows=%d): "
+            "serving exact search",
+            rows,
+            min_rows,
+        )
+        return
+    index = engine.build_index(n_lists=routed.get("n_lists"))
+    engine.nprobe = int(routed.get("nprobe", 32))
+    logger.info("routed search on: nprobe=%d, index %s", engine.nprobe, index.stats)
+
+
 def create_app(
     data_dir: Optional[str] = None,
     device: Optional[str] = None,
     engine: Optional[GfkbEngine] = None,
+    config: Optional[Any] = None,
 ) -> FastAPI:
+    """``config`` is a ``ConfigStore`` (or anything with its ``get``); its
+    ``gfkb.routed`` block opts the service into routed search."""
     app = FastAPI(title="Kakveda-AMD GFKB")
     if engine is None:
         import torch
@@ -134,6 +171,7 @@ def create_app(
             data_dir=data_dir or os.environ.get("DATA_DIR", "/app/data"), device=dev
         )
     app.state.engine = engine
+    _setup_routed(engine, config)
     # micro-batcher on by default; KAKVEDA_MATCH_BATCHER=0 opts out
     batcher = (
         MatchBatcher(engine)
@@ -172,12 +210,15 @@ def create_app(
                 req.signature_text,
                 failure_type=req.failure_type,
                 filter_first=req.filter_first,
+                exact=req.exact,
             )
         else:
+            extra = {"nprobe": 0} if req.exact else {}
             matches = engine.match(
                 req.signature_text,
                 failure_type=req.failure_type,
                 filter_first=req.filter_first,
+                **extra,
             )
         observe_gfkb(engine.store.count, len(engine.failures))
         return FailureMatchResponse(matches=matches)
