@@ -86,6 +86,14 @@ def cosine_topk(
     The HIP kernel keeps at most KMAX=8 candidates per row; a request with
     k > 8 on GPU returns the true top-8 padded with (-inf, -1) so CPU and
     GPU agree on the leading 8 columns instead of the GPU path raising.
+
+    Precondition of exactness on GPU: unit rows (|q| = |c| = 1 up to bf16
+    rounding). The streaming kernels (B <= 8, N >= 64k) admit a row when its
+    score clears the emission floor lowered by D * 2^-22, the bound on how
+    far two fp32 summation orders of one unit-row inner product can differ;
+    rows of larger norm can exceed it and lose a match that sits on the
+    floor. Equal scores are all eligible members of the result (k distinct
+    indices); which of them are returned, and in what order, is unspecified.
     """
     n = int(valid_n) if valid_n is not None else corpus.shape[0]
     B = queries.shape[0]

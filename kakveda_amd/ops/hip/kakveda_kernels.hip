@@ -205,10 +205,10 @@ std::tuple<torch::Tensor, torch::Tensor> cosine_topk_impl(
     // (its scores are bit-equal to the prepass kernel's) and cuts the
     // candidates to k/8, but measured +0.8..1.4% on the 10M bench, inside
     // the run-to-run band in two of three A/B sets, so it does not ship
-    // (profiles/knn_kernel_history.md). It must never reach the unfiltered
-    // streaming kernels: they sum in another order, may score the column
-    // that set the floor an ulp lower, and rely on the slack between the
-    // 8th and the k-th best (k < 8) to keep it.
+    // (profiles/knn_kernel_history.md). The streaming kernels sum in another
+    // order and may score the column that set the floor a few ulps lower;
+    // they lower the floor they read by the rounding bound of unit rows
+    // (kernels_impl.h streaming_floor), whatever the depth published here.
     const int floor_k = KMAX;
     const Floors f =
         p.prepass
@@ -283,11 +283,16 @@ std::tuple<torch::Tensor, torch::Tensor> cosine_topk_impl(
   // start with near-converged pruning thresholds instead of each paying
   // the bootstrap insert storm (measured: warm thresholds are worth
   // ~10% end-to-end; the sample scan is ~0.5% extra work, its partial
-  // writes land in slots the main launch overwrites).
-  if (p.prepass)
+  // writes land in slots the main launch overwrites). Because they are
+  // overwritten, the thresholds they backed must not prune equal scores:
+  // relax_rowthr lowers each strictly below its value before the main launch.
+  if (p.prepass) {
     launch_partial128(p.prepass_mode, dim3(p.preg, (B + BM - 1) / BM), a,
                       pscore.data_ptr<float>(), pidx.data_ptr<int>(), PRE_TILES,
                       ch.nchunks, thr, flt);
+    hipLaunchKernelGGL(relax_rowthr, dim3((B + 255) / 256), dim3(256), 0,
+                       a.stream, thr, B);
+  }
   if (p.main == MainKernel::Stash8p)
     launch_partial8p(p.mode, grid, a, pscore.data_ptr<float>(),
                      pidx.data_ptr<int>(), ch.chunk_tiles, ch.nchunks, thr,

@@ -62,6 +62,27 @@ __global__ void init_rowthr(unsigned* thr, int n) {
   if (i < n) thr[i] = enc_f32(NEG_INF);
 }
 
+// Lower every published threshold strictly below its value. The list
+// kernels prune with a strict `score > threshold`, which is exact while the
+// list that backs a published minimum survives: a column tied with that
+// minimum is as good as a kept one. The warming prepass's lists do NOT
+// survive (the main launch overwrites their partial slots), so after it a
+// column EQUAL to the threshold would be in nobody's list: 8 bit-identical
+// rows in one prepass list vanished from the result, and 8 distinct
+// near-duplicates at k = 8 lost the 8th. The main launch recomputes the
+// prepass's scores bit for bit (same kernel, same column -> lane mapping),
+// so any strictly lower threshold re-admits them; this steps down by about
+// two ulps, and from +-0 to -FLT_MIN (a one-code step from +0 lands on -0,
+// which compares equal to +0). NEG_INF (nothing published) stays.
+__global__ void relax_rowthr(unsigned* thr, int n) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) {
+    const float v = dec_f32(thr[i]);
+    if (v > NEG_INF)
+      thr[i] = enc_f32(v - fmaxf(fabsf(v) * 0x1p-23f, 1.17549435e-38f));
+  }
+}
+
 // Stage one [128 rows x 64 k] bf16 tile into LDS via global_load_lds.
 // LDS image is lane-linear; the 16-byte slot index is XOR-swizzled with
 // (row & 7) on the global source so the fragment reads (which apply the
@@ -1380,6 +1401,21 @@ __global__ __launch_bounds__(256) void emit_bin(
   }
 }
 
+// The streaming kernels' emission floor was scored by the MFMA prepass, the
+// rows they stream by VALU sums in another order. Both add the same exact
+// bf16 products in fp32, each within (D-1) * 2^-24 * sum|q_i c_i| of the true
+// value, which for UNIT ROWS (the precondition of the search) is
+// <= (D-1) * 2^-24: the two scores of one column differ by < D * 2^-23. The
+// floor is the 8th best of the sample, so whenever a sampled column is among
+// a query's best 8 (always, once the sample covers the corpus; and bit-equal
+// duplicates make the 8th best EQUAL the best) that difference can put the
+// column's streamed score under its own floor. Every streaming kernel
+// therefore compares against the floor lowered by twice the bound. NEG_INF
+// (no floor published) absorbs the subtraction.
+DEVINL float streaming_floor(unsigned enc_floor, int D) {
+  return dec_f32(enc_floor) - (float)D * 0x1p-22f;
+}
+
 // ---------------------------------------------------------------------------
 // Small-batch streaming emission search (B <= 8): request-level serving.
 //
@@ -1389,8 +1425,9 @@ __global__ __launch_bounds__(256) void emit_bin(
 // streams whole corpus rows (64 lanes read 64 consecutive rows — every
 // byte of HBM read exactly once, full-bandwidth pattern), keeps B <= 8
 // fp32 accumulators in registers against the LDS-resident queries, and
-// emits scores >= the per-query prepass floor into the same candidate
-// buffer the emission path merges. Exactness = the emission argument.
+// emits scores >= the per-query prepass floor (lowered: streaming_floor)
+// into the same candidate buffer the emission path merges. Exactness = the
+// emission argument.
 // ---------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void smallb_emit_kernel(
     const bf16_t* __restrict__ Q, const bf16_t* __restrict__ C, int B,
@@ -1401,7 +1438,7 @@ __global__ __launch_bounds__(256) void smallb_emit_kernel(
   __shared__ float fl[8];
   for (int i = threadIdx.x; i < B * (D / 8); i += 256)
     ((bf16x8*)qmem)[i] = ((const bf16x8*)Q)[i];
-  if (threadIdx.x < B) fl[threadIdx.x] = dec_f32(rowthr[threadIdx.x]);
+  if (threadIdx.x < B) fl[threadIdx.x] = streaming_floor(rowthr[threadIdx.x], D);
   __syncthreads();
 
   const int nj = D / 8;  // D % 64 == 0 -> nj % 8 == 0
@@ -1465,8 +1502,9 @@ __global__ __launch_bounds__(256) void smallb_emit_kernel(
 // eight same-line 16-B loads), so the win is the leaner inner loop
 // (1,587 vs 2,442 instructions) and 134-vs-186 VGPRs = 3-vs-2
 // waves/SIMD occupancy, NOT cache behaviour. Exactness: identical
-// emission contract to v2 — every score >= the shared prepass floor is
-// emitted; tail rows are clamped for the load and guarded at emission.
+// emission contract to v2 — every score >= the shared prepass floor
+// (lowered: streaming_floor) is emitted; tail rows are clamped for the load
+// and guarded at emission.
 //
 // FILTER is the label-filtered form (eligibility rule: see
 // cosine_topk_partial_t): want[0..B) sits in LDS beside fl, each row
@@ -1490,20 +1528,11 @@ __global__ __launch_bounds__(256) void smallb_emit_kernel_v4(
   (void)wl;
   for (int i = threadIdx.x; i < B * (D / 8); i += 256)
     ((bf16x8*)qmem)[i] = ((const bf16x8*)Q)[i];
-  if (threadIdx.x < B) fl[threadIdx.x] = dec_f32(rowthr[threadIdx.x]);
+  if (threadIdx.x < B) fl[threadIdx.x] = streaming_floor(rowthr[threadIdx.x], D);
   if constexpr (FILTER) {
     __shared__ int wls[8];  // no LDS in the unfiltered kernel
     if (threadIdx.x < B) wls[threadIdx.x] = want[threadIdx.x];
     wl = wls;
-    // The floor was scored by the MFMA prepass, the rows below by VALU
-    // sums in another order. Both add the same exact bf16 products in
-    // fp32, each within (D-1) * 2^-24 * sum|q_i c_i| (<= (D-1) * 2^-24 for
-    // unit rows) of the true value, so they differ by < D * 2^-23. When a
-    // sampled row IS a query's k-th best (a sparse label, or a sample that
-    // covers the whole corpus) that difference can put its streamed score
-    // under its own floor; lower the floor by twice the bound. NEG_INF
-    // (no floor published) absorbs the subtraction.
-    if (threadIdx.x < B) fl[threadIdx.x] -= (float)D * 0x1p-22f;
   }
   __syncthreads();
 

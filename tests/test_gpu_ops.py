@@ -492,6 +492,14 @@ def test_smallb_streaming_search_exact(B):
     assert (idx2 < 123457).all()
     ref2, _ = torch.topk(sims[:, :123457], 5, dim=1)
     assert torch.allclose(scores2, ref2, atol=2e-2, rtol=1e-2)
+    # k = 8: no slack between the emission floor (8th best of the sample)
+    # and the 8th match, in the sampled prefix and past it
+    scores8, idx8 = ops.cosine_topk(q, c, 8)
+    torch.cuda.synchronize()
+    ref8, _ = torch.topk(sims, 8, dim=1)
+    assert torch.allclose(scores8, ref8, atol=2e-2, rtol=1e-2)
+    assert torch.allclose(sims.gather(1, idx8), ref8, atol=1e-4)
+    assert all(len(set(r)) == 8 for r in idx8.tolist())
 
 
 @pytest.mark.gpu
