@@ -235,35 +235,88 @@ def l2normalize_(t: torch.Tensor, start_row: int = 0, end_row: Optional[int] = N
 # ---------------------------------------------------------------------------
 
 def embedding_bag(table: torch.Tensor, idx: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
-    """out[b] = sum_l w[b,l] * table[idx[b,l]]  -> [B, D] float32."""
+    """out[b] = sum_l w[b,l] * table[idx[b,l]]  -> [B, D] float32.
+
+    table bf16 [V, D], idx integer [B, L], w [B, L]; L <= 128 on GPU. An
+    index outside [0, V) contributes nothing, whatever its weight (-1 pads
+    a short bag).
+    """
     if table.device.type == "cuda":
         ext = _require_ext()
         return ext.embedding_bag(table, idx.to(torch.int32), w.float())
-    flat = table[idx.reshape(-1).long()].reshape(*idx.shape, table.shape[1]).float()
-    return (flat * w.unsqueeze(-1).float()).sum(dim=1)
+    ix = idx.long()
+    live = (ix >= 0) & (ix < table.shape[0])
+    flat = table[ix.clamp(0, table.shape[0] - 1).reshape(-1)].reshape(*idx.shape, table.shape[1]).float()
+    return (flat * (w.float() * live).unsqueeze(-1)).sum(dim=1)
 
 
 # ---------------------------------------------------------------------------
 # k-means (pattern detector)
 # ---------------------------------------------------------------------------
 
+#: LDS a block of the dedicated assignment kernel may use for its 64-row
+#: centroid image (kernels_impl.h ASSIGN_LDS_BYTES)
+_ASSIGN_LDS_BYTES = 160 * 1024
+
+#: rows per cosine_topk call on the general route of kmeans_assign_scored:
+#: one launch holds at most 65535 row tiles of 128 rows (knn_plan.h
+#: plan_fits_grid), the 10M-point detector has more
+_ASSIGN_CHUNK_ROWS = 1 << 20
+
+
+def assign_pitch(D: int) -> int:
+    """Row pitch in bytes of the assignment kernel's centroid LDS image
+    (mirror of kernels_impl.h assign_pitch; the header pins the resulting
+    D limit with a static_assert, tests/test_aux_cases_ref.py pins it here)."""
+    return D * 2 + ((64 - (D * 2) % 256) + 256) % 256
+
+
+def assign_kernel_fits(C: int, D: int) -> bool:
+    """Whether the dedicated C<=64 assignment kernel takes this shape: its
+    64 centroid rows of D dims must fit the block's LDS, which holds for
+    D <= KMEANS_ASSIGN_MAX_D."""
+    return C <= 64 and 64 * assign_pitch(D) <= _ASSIGN_LDS_BYTES
+
+
+#: widest row (a multiple of 64) the dedicated assignment kernel accepts
+KMEANS_ASSIGN_MAX_D = max(d for d in range(64, 4096 + 1, 64) if assign_kernel_fits(1, d))
+
+
 def kmeans_assign_scored(
     points: torch.Tensor, centroids: torch.Tensor
 ) -> Tuple[torch.Tensor, torch.Tensor]:
     """(top-1 cosine f32 [N], nearest centroid id i64 [N]) per point.
 
-    GPU, C<=64: the dedicated LDS-resident-centroid kernel (point stream
-    straight from HBM to MFMA, no per-window barriers — built for the
-    pattern detector's N-huge/C-tiny shape). GPU, C>64: the general fused
-    cosine_topk with k=1. CPU: eager matmul+argmax.
+    GPU, C<=64 and D<=KMEANS_ASSIGN_MAX_D (1152): the dedicated
+    LDS-resident-centroid kernel (point stream straight from HBM to MFMA,
+    no per-window barriers — built for the pattern detector's
+    N-huge/C-tiny shape). GPU otherwise (C>64, or rows too wide for the
+    LDS image): the general fused cosine_topk with k=1, in calls of at most
+    2^20 points so that no N exceeds one launch's row tiles. CPU: eager
+    matmul+argmax.
+
+    Ties: the dedicated kernel and the CPU path return the lowest index
+    among equal best scores. The general route returns one of them, which
+    one is unspecified (see cosine_topk).
     """
     if points.device.type == "cuda":
         ext = _require_ext()
-        if centroids.shape[0] <= 64:
+        C, D = int(centroids.shape[0]), int(centroids.shape[1])
+        if assign_kernel_fits(C, D):
             scores, idx = ext.kmeans_assign(points, centroids)
             return scores, idx.long()
-        scores, idx = ext.cosine_topk(points, centroids, 1, centroids.shape[0])
-        return scores[:, 0], idx[:, 0]
+        N = int(points.shape[0])
+        if N <= _ASSIGN_CHUNK_ROWS:
+            scores, idx = ext.cosine_topk(points, centroids, 1, C)
+            return scores[:, 0], idx[:, 0]
+        scores = torch.empty(N, dtype=torch.float32, device=points.device)
+        idx = torch.empty(N, dtype=torch.int64, device=points.device)
+        for r0 in range(0, N, _ASSIGN_CHUNK_ROWS):
+            r1 = min(r0 + _ASSIGN_CHUNK_ROWS, N)
+            s, i = ext.cosine_topk(points[r0:r1], centroids, 1, C)
+            scores[r0:r1] = s[:, 0]
+            idx[r0:r1] = i[:, 0]
+        return scores, idx
     sims = points.float() @ centroids.float().t()
     top = sims.max(dim=1)
     return top.values, top.indices
@@ -281,6 +334,10 @@ def kmeans_update(
 
     GPU: LDS-partial segmented-reduction HIP kernel (points read once per
     64-dim tile). CPU fallback: index_add_.
+
+    A point whose assignment is outside [0, n_clusters) is dropped from
+    sums and counts (-1 marks an unassigned point). ``counts`` is float32 and counts by adding 1.0: it is exact up to 2^24
+    points per cluster and loses the odd counts above that.
     """
     if points.device.type == "cuda" and n_clusters <= 512:
         ext = _require_ext()
@@ -288,10 +345,14 @@ def kmeans_update(
             points.to(torch.bfloat16), assign.to(torch.int32), int(n_clusters)
         )
     D = points.shape[1]
+    a = assign.long()
+    live = (a >= 0) & (a < n_clusters)
+    if not bool(live.all()):
+        a, points = a[live], points[live]
     sums = torch.zeros(n_clusters, D, dtype=torch.float32, device=points.device)
-    sums.index_add_(0, assign.long(), points.float())
+    sums.index_add_(0, a, points.float())
     counts = torch.zeros(n_clusters, dtype=torch.float32, device=points.device)
-    counts.index_add_(0, assign.long(), torch.ones_like(assign, dtype=torch.float32))
+    counts.index_add_(0, a, torch.ones_like(a, dtype=torch.float32))
     return sums, counts
 
 

@@ -1,6 +1,7 @@
 // Torch extension bindings for the kakveda kernels (see kernels_impl.h).
 #include <hip/hip_runtime.h>
 #include <torch/extension.h>
+#include <c10/hip/HIPException.h>
 #include <c10/hip/HIPStream.h>
 #include <cstdlib>
 #include <string>
@@ -189,6 +190,9 @@ std::tuple<torch::Tensor, torch::Tensor> cosine_topk_impl(
   const KnnArgs a = knn_args(queries, corpus, N);
   const int B = a.B;
   const KnnPlan p = plan_cosine_topk(B, N, k, env, allow_emission, (bool)flt);
+  TORCH_CHECK(plan_fits_grid(p, B), "cosine_topk: ", B,
+              " query rows need more than ", MAX_GRID_Y, " row tiles of ",
+              p.prepass ? BM : p.tile, " rows in one launch; split the batch");
   const Chunking& ch = p.ch;
 
   auto pscore = torch::empty({(long)B * ch.nchunks * KMAX}, a.f32());
@@ -374,6 +378,7 @@ void l2normalize_(torch::Tensor t, int64_t start_row, int64_t end_row) {
   hipLaunchKernelGGL(l2normalize_rows, dim3(blocks), dim3(THREADS), 0,
                      stream.stream(), (bf16_t*)t.data_ptr(), (int)start_row,
                      nrows, D);
+  C10_HIP_KERNEL_LAUNCH_CHECK();
 }
 
 torch::Tensor embedding_bag(torch::Tensor table, torch::Tensor idx, torch::Tensor w) {
@@ -387,11 +392,13 @@ torch::Tensor embedding_bag(torch::Tensor table, torch::Tensor idx, torch::Tenso
   TORCH_CHECK(L <= 128, "L must be <= 128");
   TORCH_CHECK(w.size(0) == B && w.size(1) == L, "w shape mismatch");
   auto out = torch::empty({B, D}, torch::TensorOptions().dtype(torch::kFloat32).device(table.device()));
+  if (B == 0 || D == 0) return out;  // nothing to launch
   auto stream = c10::hip::getCurrentHIPStream();
   hipLaunchKernelGGL(embedding_bag_kernel, dim3(B), dim3(THREADS), 0,
                      stream.stream(), (const bf16_t*)table.data_ptr(),
                      idx.data_ptr<int>(), w.data_ptr<float>(),
                      out.data_ptr<float>(), L, D, V);
+  C10_HIP_KERNEL_LAUNCH_CHECK();
   return out;
 }
 
@@ -409,16 +416,17 @@ std::tuple<torch::Tensor, torch::Tensor> kmeans_assign(
   TORCH_CHECK(D % 64 == 0, "D must be a multiple of 64");
   TORCH_CHECK(C >= 1 && C <= 64, "kmeans_assign kernel supports C<=64");
   const size_t lds = 64 * (size_t)assign_pitch(D);
-  TORCH_CHECK(lds <= 160 * 1024, "D too large for LDS-resident centroids");
+  TORCH_CHECK(lds <= ASSIGN_LDS_BYTES, "D too large for LDS-resident centroids");
   auto opts_f = torch::TensorOptions().dtype(torch::kFloat32).device(points.device());
   auto opts_i = torch::TensorOptions().dtype(torch::kInt32).device(points.device());
   auto score = torch::empty({N}, opts_f);
   auto idx = torch::empty({N}, opts_i);
+  if (N == 0) return {score, idx};  // nothing to launch
   static bool attr_set = false;
   if (!attr_set) {
     (void)hipFuncSetAttribute((const void*)kmeans_assign_kernel,
                               hipFuncAttributeMaxDynamicSharedMemorySize,
-                              160 * 1024);
+                              ASSIGN_LDS_BYTES);
     attr_set = true;
   }
   const long ntiles = (N + 255) / 256;
@@ -429,6 +437,7 @@ std::tuple<torch::Tensor, torch::Tensor> kmeans_assign(
                      (const bf16_t*)centroids.data_ptr(),
                      score.data_ptr<float>(), idx.data_ptr<int>(), (int)N, D,
                      C);
+  C10_HIP_KERNEL_LAUNCH_CHECK();
   return {score, idx};
 }
 
@@ -460,6 +469,7 @@ std::tuple<torch::Tensor, torch::Tensor> kmeans_update(
   auto opts = torch::TensorOptions().dtype(torch::kFloat32).device(points.device());
   auto sums = torch::zeros({C, D}, opts);
   auto counts = torch::zeros({C}, opts);
+  if (N == 0) return {sums, counts};  // nothing to launch
   // chunk so the grid oversubscribes the CUs
   const int dim_tiles = D / 64;
   int chunks = std::max(1, 2048 / dim_tiles);
@@ -471,6 +481,7 @@ std::tuple<torch::Tensor, torch::Tensor> kmeans_update(
                      (const bf16_t*)points.data_ptr(), assign.data_ptr<int>(),
                      sums.data_ptr<float>(), counts.data_ptr<float>(), N, D, C,
                      ppc);
+  C10_HIP_KERNEL_LAUNCH_CHECK();
   return {sums, counts};
 }
 
@@ -733,4 +744,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("valid_n"), pybind11::arg("n_indexed"),
         pybind11::arg("max_list_len") = (int64_t)0);
   m.attr("KMAX") = KMAX;
+  // the widest row the C<=64 assignment kernel can keep resident in LDS
+  m.attr("KMEANS_ASSIGN_MAX_D") = kmeans_assign_max_d();
 }

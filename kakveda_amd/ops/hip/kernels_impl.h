@@ -1693,8 +1693,12 @@ __global__ __launch_bounds__(256) void emit_merge_topk(
 // k-means centroid update: segmented reduction of bf16 points into
 // per-cluster fp32 sums + counts. Grid: (dim-tiles, point-chunks); each
 // block accumulates a [C][64]-dim LDS partial over its point chunk, then
-// adds it to the global sums once (C <= 256; LDS = C*64*4 <= 64 KiB).
-// Points are read exactly once per dim-tile (coalesced 128-B row slices);
+// adds it to the global sums once. C <= 512. C <= 128 keeps R = 4 replicas
+// of the partial (one per point lane, no atomics), C > 128 keeps R = 1 and
+// adds with LDS atomics; LDS = (R*C*64 + C)*4 bytes, the [C] tail being the
+// counts partial: 128.5 KiB at C = 128, 130 KiB at C = 512, so the binding raises
+// the dynamic LDS cap above 64 KiB when needed. Points whose assignment is
+// outside [0, C) are dropped from sums and counts. Points are read exactly once per dim-tile (coalesced 128-B row slices);
 // bandwidth-bound by design, replacing torch index_add_ (which was ~30x
 // over the I/O floor in benchmarks/kmeans_bench.py).
 // ---------------------------------------------------------------------------
@@ -2001,6 +2005,24 @@ constexpr int ASSIGN_THREADS = 512;  // 8 waves
 constexpr __host__ __device__ int assign_pitch(int D) {
   return D * 2 + ((64 - (D * 2) % 256) + 256) % 256;
 }
+
+// The 64-row centroid image must fit the 160 KiB of LDS a block can have,
+// which bounds D: 1152 is the widest row that fits, 1216 the first that
+// does not. ops.kmeans_assign_scored mirrors this rule to send wider rows
+// (and C > 64) to the general cosine_topk kernels instead
+// (kakveda_amd/ops/__init__.py assign_kernel_fits, pinned by
+// tests/test_aux_cases_ref.py).
+constexpr int ASSIGN_LDS_BYTES = 160 * 1024;
+constexpr __host__ __device__ bool assign_fits_lds(int D) {
+  return 64 * assign_pitch(D) <= ASSIGN_LDS_BYTES;
+}
+constexpr int kmeans_assign_max_d() {
+  int d = 64;
+  while (assign_fits_lds(d + 64)) d += 64;
+  return d;
+}
+static_assert(kmeans_assign_max_d() == 1152 && !assign_fits_lds(1216),
+              "update KMEANS_ASSIGN_MAX_D in kakveda_amd/ops/__init__.py");
 
 __global__ __launch_bounds__(ASSIGN_THREADS, 1) void kmeans_assign_kernel(
     const bf16_t* __restrict__ P, const bf16_t* __restrict__ Cc,

@@ -136,6 +136,20 @@ struct KnnPlan {
   MergeKernel merge;
 };
 
+// Every main launch and every prepass puts its row tiles on grid.y, which
+// the device limits to MAX_GRID_Y blocks. The prepass runs the 128-row-tile
+// kernel under either main tile, so it needs ceil(B / BM) rows of blocks
+// whatever p.tile is. A plan that does not fit is refused by the caller
+// before anything is allocated or launched: a launch over the limit fails
+// without running, and its outputs would be returned uninitialised.
+constexpr int MAX_GRID_Y = 65535;
+
+inline bool plan_fits_grid(const KnnPlan& p, int B) {
+  if (p.ch.row_tiles < 1 || p.ch.row_tiles > MAX_GRID_Y) return false;
+  if (p.prepass && ((long)B + BM - 1) / BM > MAX_GRID_Y) return false;
+  return true;
+}
+
 // Label-filtered search (cosine_topk_filtered). Only two kernels carry the
 // filter: the streaming small-batch kernel (v4) and the 128x128 mode-11
 // list kernel, which also runs every prepass. So the filtered table is

@@ -160,6 +160,45 @@ int main() {
   CHECK(c.row_tiles == 8 && c.ntiles == 39063 && c.chunk_tiles == 128 &&
         c.nchunks == 312);
 
+  // grid.y holds at most 65535 row tiles. 128-row tile: the k = 1 argmax
+  // plan of the k-means caller (huge B, a handful of centroids).
+  {
+    const int fit = MAX_GRID_Y * BM;  // 8 388 480 rows
+    const KnnPlan ok = plan_cosine_topk(fit, 200, 1, env_of(none), true);
+    CHECK(ok.main == A && ok.tile == 128 && ok.ch.row_tiles == 65535);
+    CHECK(plan_fits_grid(ok, fit));
+    const KnnPlan over = plan_cosine_topk(fit + 1, 200, 1, env_of(none), true);
+    CHECK(over.tile == 128 && over.ch.row_tiles == 65536);
+    CHECK(!plan_fits_grid(over, fit + 1));
+    // the list kernel at k > 1 on the same tile
+    CHECK(plan_fits_grid(plan_cosine_topk(fit, 200, 5, env_of(none), true), fit));
+    CHECK(!plan_fits_grid(plan_cosine_topk(fit + 1, 200, 5, env_of(none), true), fit + 1));
+  }
+  // 256-row tile without a prepass (8pbl): twice as many rows fit
+  {
+    const int fit = MAX_GRID_Y * BM8;  // 16 776 960 rows
+    const KnnPlan ok = plan_cosine_topk(fit, 4096, 5, env_of(sel("8pbl")), true);
+    CHECK(ok.main == S && ok.tile == 256 && ok.ch.row_tiles == 65535 && !ok.prepass);
+    CHECK(plan_fits_grid(ok, fit));
+    const KnnPlan over = plan_cosine_topk(fit + 1, 4096, 5, env_of(sel("8pbl")), true);
+    CHECK(over.tile == 256 && over.ch.row_tiles == 65536);
+    CHECK(!plan_fits_grid(over, fit + 1));
+  }
+  // 256-row tile with the emission prepass: the prepass runs on 128-row
+  // tiles, so its limit is the 128-row one although the main launch fits
+  {
+    const int fit = MAX_GRID_Y * BM;
+    const KnnPlan ok = plan_cosine_topk(fit, 65536, 5, env_of(none), true);
+    CHECK(ok.main == E && ok.tile == 256 && ok.prepass);
+    CHECK(plan_fits_grid(ok, fit));
+    const KnnPlan over = plan_cosine_topk(fit + 1, 65536, 5, env_of(none), true);
+    CHECK(over.main == E && over.prepass && over.ch.row_tiles == 32768);
+    CHECK(!plan_fits_grid(over, fit + 1));
+  }
+  // everyday shapes fit
+  CHECK(plan_fits_grid(plan_cosine_topk(1, 100, 5, env_of(none), true), 1));
+  CHECK(plan_fits_grid(plan_cosine_topk(2048, 10000000, 5, env_of(none), true), 2048));
+
   if (failures) {
     std::printf("%d check(s) failed\n", failures);
     return 1;
