@@ -87,11 +87,12 @@ Partial8pFn partial8p_kernel(int mode) {
 // 9/15) and null/0 otherwise.
 void launch_partial8p(int mode, dim3 grid, const KnnArgs& a, float* pscore,
                       int* pidx, int chunk_tiles, int nchunks, unsigned* rowthr,
-                      unsigned long long* eseg, unsigned* esegcnt, long segcap) {
+                      unsigned long long* eseg, unsigned* esegcnt, long segcap,
+                      int tile_first = 0) {
   hipLaunchKernelGGL(partial8p_kernel(mode), grid, dim3(THREADS8), 0, a.stream,
                      a.q, a.c, pscore, pidx, a.B, a.N, a.D, chunk_tiles, nchunks,
                      rowthr, (unsigned long long*)nullptr, (float*)nullptr, eseg,
-                     esegcnt, segcap, (char*)nullptr);
+                     esegcnt, segcap, (char*)nullptr, tile_first);
 }
 
 torch::Tensor new_rowthr(const KnnArgs& a) {
@@ -144,15 +145,25 @@ Floors run_emission_floors(const KnnArgs& a, int preg, int prepass_mode, int k,
 // Emission outputs: per-row candidate buffer + counts. The 8p main kernel
 // (seg > 0) also gets one record segment and one record count per block
 // (see kernels_impl.h EPI_MODE 9 and emit_bin); every block writes its
-// count, so neither needs clearing.
+// count, so neither needs clearing. The candidate lists start empty, or,
+// given the sample's top-KMAX (`seed`: the main launch will skip the sampled
+// columns), hold exactly those: emit_seed then writes every count, in the
+// place of the clearing memset.
 struct EmitBufs {
   torch::Tensor cand, ccount, eseg, esegcnt;
 };
 
 EmitBufs new_emit_bufs(const KnnArgs& a, long cap, const Chunking& ch,
-                       long seg = 0) {
+                       long seg = 0, const Floors* seed = nullptr) {
   EmitBufs e{torch::empty({(long)a.B, cap}, a.i64()),
-             torch::zeros({a.B}, a.i32()), {}, {}};
+             seed ? torch::empty({a.B}, a.i32()) : torch::zeros({a.B}, a.i32()),
+             {}, {}};
+  if (seed)
+    hipLaunchKernelGGL(emit_seed, dim3((a.B + 255) / 256), dim3(256), 0,
+                       a.stream, seed->samp_s.data_ptr<float>(),
+                       (const long*)seed->samp_i.data_ptr<int64_t>(), a.B,
+                       (unsigned long long*)e.cand.data_ptr<int64_t>(),
+                       (unsigned*)e.ccount.data_ptr<int>(), cap);
   if (seg > 0) {
     const long blocks = (long)ch.nchunks * ch.row_tiles;
     e.eseg = torch::empty({blocks, seg}, a.i64());
@@ -164,24 +175,29 @@ EmitBufs new_emit_bufs(const KnnArgs& a, long cap, const Chunking& ch,
 // The 8p emission main launch and its binning step: afterwards cand/ccount
 // hold what the per-row scatter of earlier versions left there (candidate
 // order within a row apart, which emit_merge_topk does not depend on).
+// `ch` chunks the column tiles from `tile_first` on; pscore/pidx need
+// [B][ch.nchunks][KMAX] entries (padded chunks write -inf partials).
 void launch_emit8p(int mode, const KnnArgs& a, const Chunking& ch,
                    torch::Tensor& pscore, torch::Tensor& pidx,
                    const torch::Tensor& rowthr, EmitBufs& e, long cap,
-                   long seg) {
+                   long seg, int tile_first = 0) {
   TORCH_CHECK(seg > 0 && ch.chunk_tiles <= 128,
               "emission segments need seg > 0 and chunk_tiles <= 128");
+  TORCH_CHECK(pscore.numel() >= (long)a.B * ch.nchunks * KMAX &&
+                  pidx.numel() >= (long)a.B * ch.nchunks * KMAX,
+              "partial buffers are smaller than the main launch's chunks");
   unsigned long long* const eseg = (unsigned long long*)e.eseg.data_ptr<int64_t>();
   unsigned* const esegcnt = (unsigned*)e.esegcnt.data_ptr<int>();
   launch_partial8p(mode, dim3(ch.nchunks, ch.row_tiles), a,
                    pscore.data_ptr<float>(), pidx.data_ptr<int>(),
                    ch.chunk_tiles, ch.nchunks, (unsigned*)rowthr.data_ptr<int>(),
-                   eseg, esegcnt, seg);
+                   eseg, esegcnt, seg, tile_first);
   hipLaunchKernelGGL(emit_bin, dim3(ch.nchunks, ch.row_tiles), dim3(256), 0,
                      a.stream, (const unsigned long long*)eseg,
                      (const unsigned*)esegcnt, (int)seg, ch.chunk_tiles,
                      ch.nchunks, a.B, a.N,
                      (unsigned long long*)e.cand.data_ptr<int64_t>(),
-                     (unsigned*)e.ccount.data_ptr<int>(), cap);
+                     (unsigned*)e.ccount.data_ptr<int>(), cap, tile_first);
 }
 
 std::tuple<torch::Tensor, torch::Tensor> cosine_topk_impl(
@@ -195,8 +211,11 @@ std::tuple<torch::Tensor, torch::Tensor> cosine_topk_impl(
               p.prepass ? BM : p.tile, " rows in one launch; split the batch");
   const Chunking& ch = p.ch;
 
-  auto pscore = torch::empty({(long)B * ch.nchunks * KMAX}, a.f32());
-  auto pidx = torch::empty({(long)B * ch.nchunks * KMAX}, a.i32());
+  // [B][nchunks][KMAX] for whichever launch has more chunks (the emission
+  // main launch over p.mch writes only its padded chunks' -inf partials)
+  const long pslots = (long)B * std::max(ch.nchunks, p.mch.nchunks) * KMAX;
+  auto pscore = torch::empty({pslots}, a.f32());
+  auto pidx = torch::empty({pslots}, a.i32());
   auto out_score = torch::empty({B, k}, a.f32());
   auto out_idx = torch::empty({B, k}, a.i64());
   const dim3 grid(ch.nchunks, ch.row_tiles);
@@ -218,7 +237,11 @@ std::tuple<torch::Tensor, torch::Tensor> cosine_topk_impl(
         p.prepass
             ? run_emission_floors(a, p.preg, p.prepass_mode, floor_k, flt)
             : Floors{new_rowthr(a), {}, {}};
-    EmitBufs e = new_emit_bufs(a, p.cap, ch, p.seg);
+    // The Emit8p main launch starts after the sampled columns
+    // (p.skip_tiles, knn_plan.h main_geometry): the sample's top-KMAX are
+    // seeded into the candidate lists in their place.
+    const bool seeded = p.skip_tiles > 0;
+    EmitBufs e = new_emit_bufs(a, p.cap, p.mch, p.mseg, seeded ? &f : nullptr);
     if (p.main == MainKernel::SmallB && flt) {
       hipLaunchKernelGGL(smallb_emit_kernel_v4<true>, dim3(p.smallb_blocks),
                          dim3(256), (size_t)B * a.D * 2, a.stream, a.q, a.c, B,
@@ -246,7 +269,8 @@ std::tuple<torch::Tensor, torch::Tensor> cosine_topk_impl(
                            (unsigned*)e.ccount.data_ptr<int>(), p.cap,
                            (const int*)nullptr, (const int*)nullptr);
     } else {
-      launch_emit8p(p.mode, a, ch, pscore, pidx, f.rowthr, e, p.cap, p.seg);
+      launch_emit8p(p.mode, a, p.mch, pscore, pidx, f.rowthr, e, p.cap, p.mseg,
+                    p.skip_tiles);
     }
     hipLaunchKernelGGL(emit_merge_topk, dim3(B), dim3(256), 0, a.stream,
                        (const unsigned long long*)e.cand.data_ptr<int64_t>(),
@@ -261,9 +285,10 @@ std::tuple<torch::Tensor, torch::Tensor> cosine_topk_impl(
       printf("emit: rows=%d max=%ld mean=%.1f cap=%ld%s\n", B, mx,
              e.ccount.to(torch::kFloat32).mean().item<float>(), p.cap,
              mx > p.cap ? "  FALLBACK" : "");
-      if (p.seg > 0)
-        printf("emit: segments=%ld max=%d seg=%ld\n", (long)e.esegcnt.size(0),
-               e.esegcnt.max().item<int>(), p.seg);
+      if (p.mseg > 0)
+        printf("emit: segments=%ld max=%d seg=%ld skip_tiles=%d\n",
+               (long)e.esegcnt.size(0), e.esegcnt.max().item<int>(), p.mseg,
+               p.skip_tiles);
     }
     if (mx > p.cap) {
       static bool warned = false;

@@ -716,7 +716,9 @@ DEVINL unsigned lds_add_rtn(unsigned* word, unsigned v) {
 // the slots, and types, of the per-row candidate buffer the kernel once
 // scattered into itself). `stats`, `slab` and `unused` are unused (they
 // belonged to pruned modes and to the global stash) and stay in the
-// signature so kernel symbols and kernarg offsets do not move.
+// signature so the kernarg offsets of the others do not move. `tile_first`
+// (modes 9/15; the other modes ignore it) is the column tile the launch
+// starts at: chunk 0 begins there.
 template <int EPI_MODE>
 __global__ __launch_bounds__(THREADS8, 2) void cosine_topk_partial8p_t(
     const bf16_t* __restrict__ Q, const bf16_t* __restrict__ C,
@@ -726,7 +728,7 @@ __global__ __launch_bounds__(THREADS8, 2) void cosine_topk_partial8p_t(
     float* __restrict__ slab = nullptr,
     unsigned long long* __restrict__ eseg = nullptr,
     unsigned* __restrict__ esegcnt = nullptr, long segcap = 0,
-    char* __restrict__ unused = nullptr) {
+    char* __restrict__ unused = nullptr, int tile_first = 0) {
   constexpr bool EMIT = EPI_MODE == 9 || EPI_MODE == 12 || EPI_MODE == 15;
   constexpr bool GEMM_ONLY = EPI_MODE == 1 || EPI_MODE == 16;
   // staggered wave groups: only for the modes whose epilogue has no
@@ -776,14 +778,18 @@ __global__ __launch_bounds__(THREADS8, 2) void cosine_topk_partial8p_t(
   const int row0 = row_tile * BM8;
   const long rb = (long)D * 2;
   const int ntiles_total = (N + BN8 - 1) / BN8;
-  const int tile0 = chunk_id * chunk_tiles;
+  constexpr bool APPEND = EPI_MODE == 9 || EPI_MODE == 15;
+  // the emission main launch starts at column tile `tile_first` (the tiles
+  // before it are the prepass sample's: knn_plan.h main_geometry); chunk
+  // ids, segments and in-chunk columns count from there. Every other mode
+  // scans from tile 0.
+  const int tile0 = (APPEND ? tile_first : 0) + chunk_id * chunk_tiles;
   const int tiles_here = min(chunk_tiles, ntiles_total - tile0);
   const int nkt = D / 64;  // windows per col tile
 
   // emission append state (modes 9/15): this wave's stash slice, the
   // block's record cursor (an LDS word behind the stashes) and the block's
   // segment of the global record buffer, indexed by (row_tile, chunk_id)
-  constexpr bool APPEND = EPI_MODE == 9 || EPI_MODE == 15;
   // (lambdas: the other modes' instruction streams must not see them)
   auto estash = [&]() -> char* {
     return smem0 + ESTASH_OFF + wid * ESTASH_WAVE;
@@ -1377,13 +1383,14 @@ __global__ __launch_bounds__(256) void emit_bin(
     const unsigned long long* __restrict__ eseg,
     const unsigned* __restrict__ esegcnt, int segcap, int chunk_tiles,
     int nchunks, int B, int N, unsigned long long* __restrict__ cand,
-    unsigned* __restrict__ ccount, long ccap) {
+    unsigned* __restrict__ ccount, long ccap, int tile_first = 0) {
   const int chunk_id = blockIdx.x, row_tile = blockIdx.y;
   const size_t segid = (size_t)row_tile * nchunks + chunk_id;
   const unsigned cnt = esegcnt[segid];
   if (cnt == 0) return;
   const int row0 = row_tile * BM8;
-  const int colbase = chunk_id * chunk_tiles * BN8;
+  // tile_first: the main launch's first column tile (its chunk 0 starts there)
+  const int colbase = (tile_first + chunk_id * chunk_tiles) * BN8;
   if (cnt > (unsigned)segcap && threadIdx.x == 0)
     atomicAdd(&ccount[row0], (unsigned)ccap + 1u);
   const unsigned n = min(cnt, (unsigned)segcap);
@@ -1399,6 +1406,34 @@ __global__ __launch_bounds__(256) void emit_bin(
       cand[(size_t)row * ccap + pos] =
           (rec & 0xffffffff00000000ull) | (unsigned)(0x7fffffff - col);
   }
+}
+
+// ---------------------------------------------------------------------------
+// Seeds each row's candidate list with the sample's top-KMAX (samp_s/samp_i,
+// run_emission_floors), packed as emit_bin packs, and sets the row's count
+// to the number seeded: the main launch then starts after the sampled
+// columns (knn_plan.h main_geometry). Empty slots (-inf, -1: fewer than KMAX
+// sampled columns survived) are left out. One thread per row; runs where
+// the counts were cleared, ahead of the main launch on the same stream.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void emit_seed(
+    const float* __restrict__ samp_s, const long* __restrict__ samp_i, int B,
+    unsigned long long* __restrict__ cand, unsigned* __restrict__ ccount,
+    long ccap) {
+  const int row = blockIdx.x * blockDim.x + threadIdx.x;
+  if (row >= B) return;
+  unsigned n = 0;
+#pragma unroll
+  for (int q = 0; q < KMAX; ++q) {
+    const float s = samp_s[(size_t)row * KMAX + q];
+    const long col = samp_i[(size_t)row * KMAX + q];
+    if (col < 0 || !(s > NEG_INF)) continue;
+    const unsigned pos = n++;
+    if (pos < (unsigned)ccap)
+      cand[(size_t)row * ccap + pos] = ((unsigned long long)enc_f32(s) << 32) |
+                                       (unsigned)(0x7fffffff - (int)col);
+  }
+  ccount[row] = n;
 }
 
 // The streaming kernels' emission floor was scored by the MFMA prepass, the

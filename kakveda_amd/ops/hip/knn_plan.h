@@ -38,6 +38,7 @@ struct KnnEnv {
   long cap = 32768;              // KAKVEDA_KNN_EMIT_CAP
   long seg = 0;                  // KAKVEDA_KNN_EMIT_SEG (<= 0: default)
   bool emit_debug = false;       // KAKVEDA_KNN_EMIT_DEBUG=1
+  bool skip_sample = true;       // KAKVEDA_KNN_SKIP_SAMPLE: 1 (default), 0
 };
 
 // `get` is std::getenv or anything with its signature.
@@ -72,6 +73,14 @@ KnnEnv parse_knn_env(GetEnv&& get) {
   if ((v = get("KAKVEDA_KNN_EMIT_CAP"))) e.cap = std::atol(v);
   if ((v = get("KAKVEDA_KNN_EMIT_SEG"))) e.seg = std::atol(v);
   if ((v = get("KAKVEDA_KNN_EMIT_DEBUG"))) e.emit_debug = v[0] == '1';
+  v = get("KAKVEDA_KNN_SKIP_SAMPLE");
+  const std::string sk = v ? v : "";
+  if (sk == "0") e.skip_sample = false;
+  else if (!sk.empty() && sk != "1")
+    throw std::runtime_error("KAKVEDA_KNN_SKIP_SAMPLE='" + sk +
+                             "' is not a setting; accepted: 1 (default: the "
+                             "emission main launch starts after the sampled "
+                             "columns), 0 (it scans the whole corpus)");
   return e;
 }
 
@@ -85,16 +94,21 @@ struct Chunking {
 // oversubscribes 256 CUs (2 blocks/CU at 128x128, 1 block/CU at 256x256).
 constexpr long default_target(int tile) { return tile == BM8 ? 512 : 2048; }
 
-inline Chunking chunking(int B, int N, int tile, long target) {
+// The same geometry over `ntiles` column tiles.
+inline Chunking chunking_tiles(int row_tiles, int ntiles, long target) {
   Chunking c;
-  c.row_tiles = (B + tile - 1) / tile;
-  c.ntiles = (N + tile - 1) / tile;
+  c.row_tiles = row_tiles;
+  c.ntiles = ntiles;
   const long want = ((long)c.ntiles * c.row_tiles + target - 1) / target;
   c.chunk_tiles = (int)std::max(4L, std::min(want, 128L));
   // pad the chunk count to a multiple of 8 so the in-kernel XCD remap is
   // bijective; padded chunks have no tiles and emit -inf partials.
   c.nchunks = ((c.ntiles + c.chunk_tiles - 1) / c.chunk_tiles + 7) & ~7;
   return c;
+}
+
+inline Chunking chunking(int B, int N, int tile, long target) {
+  return chunking_tiles((B + tile - 1) / tile, (N + tile - 1) / tile, target);
 }
 
 // Emission record segments (8-phase emission main kernel): each block
@@ -134,7 +148,91 @@ struct KnnPlan {
   long seg;              // emission records per block segment (Emit8p)
   int smallb_blocks;     // SmallB grid.x
   MergeKernel merge;
+  // The Emit8p main launch as it is launched (main_geometry below). Under
+  // every other main kernel: skip_tiles 0, mch == ch, mseg == seg.
+  int skip_tiles;  // leading BN8-column tiles left to the prepass sample
+  Chunking mch;    // chunking of the other ntiles - skip_tiles tiles
+  long mseg;       // records per block segment of that launch
 };
+
+// Makespan model of an 8-phase main launch, in column tiles per CU. The
+// kernel runs one block per CU (its LDS), 32 CUs per XCD, and hands each XCD
+// nchunks / 8 consecutive chunks times every row tile (its XCD remap; a grid
+// under 256 blocks is dealt round-robin, which spreads chunks the same way).
+// nchunks is the real chunk count R rounded up to 8, so fewer than 8 chunks
+// are padding and the busiest XCD has ceil(R / 8) real chunks wherever the
+// padding falls: it runs ceil(ceil(R / 8) * row_tiles / 32) rounds of
+// chunk_tiles tiles. The ideal is ntiles * row_tiles / 256.
+inline long model_makespan(const Chunking& c) {
+  if (c.ntiles <= 0) return 0;
+  const long real = (c.ntiles + c.chunk_tiles - 1) / c.chunk_tiles;
+  const long per_xcd = (real + 7) / 8 * c.row_tiles;
+  return (long)c.chunk_tiles * ((per_xcd + 31) / 32);
+}
+
+// Chunking of the emission main launch over `ntiles` tiles: the chunk size
+// in [4, 128] (the record's 15-bit column field caps it) with the smallest
+// modelled makespan, so that the last round of blocks is as full as the
+// tile count allows. Above ~4M rows the 128 cap, not the target, used to
+// decide the block count, and the grid ended in a partly filled round (10M
+// x 2048: 312 chunks of 128 = 10 rounds of 128 tiles where 320 chunks of
+// 119 are 10 rounds of 119). The search starts at half the chunk size the
+// target rule gives (`from` is that rule's chunking of these tiles, `whole`
+// the whole-corpus chunking), which bounds the per-block cost the model
+// leaves out (prologue, pipeline fill, tail drain: well under one tile);
+// both rule sizes are candidates, so the result never models slower than
+// either. Ties go to the larger chunk.
+inline Chunking balanced_chunking(const Chunking& from, const Chunking& whole) {
+  Chunking best = from;
+  if (from.ntiles <= 0) return best;
+  const int lo = std::max(4, std::min(from.chunk_tiles, whole.chunk_tiles) / 2);
+  for (int ct = lo; ct <= 128; ++ct) {
+    Chunking c = from;
+    c.chunk_tiles = ct;
+    c.nchunks = ((c.ntiles + ct - 1) / ct + 7) & ~7;
+    const long m = model_makespan(c), b = model_makespan(best);
+    if (m < b || (m == b && ct > best.chunk_tiles)) best = c;
+  }
+  return best;
+}
+
+// Main launch geometry of the unfiltered Emit8p plan. The prepass has
+// already scored the first preg * PRE_TILES * BN columns, its scores are
+// bit-equal to the 8-phase kernel's, and the exact top-KMAX of that sample
+// (samp_s/samp_i, whose KMAX-th is the emission floor) is in hand. For
+// k <= KMAX the corpus top-k lies in (top-KMAX of the sample) U (unsampled
+// columns scoring >= floor), so the main launch starts at the first
+// unsampled tile and the host seeds the candidate lists from the sample.
+// The remaining tiles are chunked into whole rounds of blocks
+// (balanced_chunking above) and the segments are sized from that geometry
+// (emit_seg_cap: never more bytes than the candidate buffer).
+// Nothing is skipped
+//   - when the sample covers the corpus (N <= preg * 1024): the main launch
+//     would have nothing left, and with it the record segments, emit_bin and
+//     their overflow fallback would leave the path of every request that
+//     small; those stay on the whole-corpus launch, second scan included
+//     (dropping that launch is left open);
+//   - under SmallB: the streaming kernels sum in another order, so their
+//     score of a sampled column is not bit-equal to the prepass's (a column
+//     could be seeded and emitted, or miss both, at the floor);
+//   - on the filtered path, which has no 8-phase kernel;
+//   - without a prepass, or with KAKVEDA_KNN_SKIP_SAMPLE=0, which restores
+//     the whole-corpus scan over p.ch.
+// No field above these three changes with any of this.
+inline void main_geometry(KnnPlan& p, int B, const KnnEnv& env) {
+  p.skip_tiles = 0;
+  p.mch = p.ch;
+  p.mseg = p.seg;
+  if (p.main != MainKernel::Emit8p || !p.prepass || !env.skip_sample) return;
+  const int sampled = p.preg * (PRE_TILES * BN / BN8);
+  if (sampled >= p.ch.ntiles) return;
+  p.skip_tiles = sampled;
+  p.mch = balanced_chunking(
+      chunking_tiles(p.ch.row_tiles, p.ch.ntiles - p.skip_tiles,
+                     env.target > 0 ? env.target : default_target(BM8)),
+      p.ch);
+  p.mseg = emit_seg_cap(B, env.cap, p.mch, env.seg);
+}
 
 // Every main launch and every prepass puts its row tiles on grid.y, which
 // the device limits to MAX_GRID_Y blocks. The prepass runs the 128-row-tile
@@ -180,6 +278,7 @@ inline KnnPlan plan_cosine_topk_filtered(int B, int N, int k, const KnnEnv& env,
   p.merge = emit                          ? MergeKernel::Emit
             : p.ch.nchunks * KMAX <= 1024 ? MergeKernel::Small
                                           : MergeKernel::Merge;
+  main_geometry(p, B, env);  // skips nothing: no 8-phase kernel here
   return p;
 }
 
@@ -254,6 +353,7 @@ inline KnnPlan plan_cosine_topk(int B, int N, int k, const KnnEnv& env,
   p.merge = emit                             ? MergeKernel::Emit
             : p.ch.nchunks * KMAX <= 1024    ? MergeKernel::Small
                                              : MergeKernel::Merge;
+  main_geometry(p, B, env);
   return p;
 }
 

@@ -1,0 +1,43 @@
+"""CPU check of the emission main launch geometry in the dispatch plan.
+
+Like tests/test_knn_emit_seg.py: the plan is a pure host header, so the rule
+that the 8-phase emission main launch starts after the prepass sample (which
+tiles it skips, how the rest is chunked, how its record segments are sized,
+and the KAKVEDA_KNN_SKIP_SAMPLE parsing) is compiled into a stand-alone
+program (tests/host/knn_main_geom_test.cpp) with the host C++ compiler under
+AddressSanitizer + UBSan and run here — no GPU, no torch.
+"""
+
+import os
+import shutil
+import subprocess
+
+import pytest
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SRC = os.path.join(REPO, "tests", "host", "knn_main_geom_test.cpp")
+INC = os.path.join(REPO, "kakveda_amd", "ops", "hip")
+
+
+def _compiler():
+    for cxx in ("c++", "g++", "clang++", "/opt/rocm/llvm/bin/clang++"):
+        path = shutil.which(cxx)
+        if path:
+            return path
+    return None
+
+
+def test_knn_main_launch_geometry(tmp_path):
+    cxx = _compiler()
+    if cxx is None:
+        pytest.skip("no host C++ compiler")
+    exe = str(tmp_path / "knn_main_geom_test")
+    build = subprocess.run(
+        [cxx, "-std=c++17", "-O1", "-fsanitize=address,undefined",
+         "-fno-sanitize-recover=all", "-I", INC, SRC, "-o", exe],
+        capture_output=True, text=True, timeout=300,
+    )
+    assert build.returncode == 0, build.stderr[-3000:]
+    run = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert run.returncode == 0, (run.stdout + run.stderr)[-3000:]
+    assert "cases passed" in run.stdout

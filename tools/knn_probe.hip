@@ -102,7 +102,7 @@ int main(int argc, char** argv) {
                          c8p.chunk_tiles, c8p.nchunks, rowthr,
                          (unsigned long long*)nullptr, (float*)nullptr,
                          (unsigned long long*)nullptr, (unsigned*)nullptr, 0L,
-                         (char*)nullptr);
+                         (char*)nullptr, 0);  // from column tile 0
     hipError_t le = hipGetLastError();
     if (le != hipSuccess)
       fprintf(stderr, "launch error (%s): %s\n", e.name, hipGetErrorString(le));
