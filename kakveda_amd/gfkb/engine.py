@@ -221,7 +221,8 @@ class EmbeddingStore:
         return max(self.count - index.n_indexed, 0) / float(index.n_indexed)
 
     def _search_routed(
-        self, q: torch.Tensor, k: int, count: int, nprobe: int, index
+        self, q: torch.Tensor, k: int, count: int, nprobe: int, index,
+        batched: Optional[bool] = None,
     ) -> Tuple[torch.Tensor, torch.Tensor]:
         tail = self.count - index.n_indexed
         if not self._stale_warned and tail > STALE_WARN_FRACTION * index.n_indexed:
@@ -247,6 +248,7 @@ class EmbeddingStore:
             count,
             index.n_indexed,
             index.max_list_len,
+            batched=batched,
         )
 
     def search(
@@ -257,6 +259,7 @@ class EmbeddingStore:
         want: Optional[torch.Tensor] = None,
         nprobe: Optional[int] = None,
         index=None,
+        batched: Optional[bool] = None,
     ) -> Tuple[torch.Tensor, torch.Tensor]:
         """Top-k over the first ``valid_n`` rows (default: the live count).
         Passing a snapshot of ``count`` makes the search safe to run
@@ -275,7 +278,9 @@ class EmbeddingStore:
         by the exact filtered search whatever ``nprobe`` says: exact is
         never worse, and a filtered query is not silently routed. ``index``
         is the index to route through (default: the attached one), for
-        callers that snapshot it together with ``valid_n``."""
+        callers that snapshot it together with ``valid_n``. ``batched``
+        picks the routed scan kernel (``ops.ivf_scan_topk``: None chooses by
+        batch size); it changes no result beyond fp32 summation order."""
         q = queries.to(self.dtype)
         count = self.count if valid_n is None else min(int(valid_n), self.count)
         if nprobe is not None and int(nprobe) < 0:
@@ -288,7 +293,7 @@ class EmbeddingStore:
                     "call build_index() first"
                 )
             if want is None and count > 0:
-                return self._search_routed(q, k, count, int(nprobe), index)
+                return self._search_routed(q, k, count, int(nprobe), index, batched)
         segs = self._live_segments(count)
         w = None if want is None else want.to(device=self.device, dtype=torch.int32)
 

@@ -18,7 +18,12 @@ Kernels (kakveda_amd/ops/hip/):
 - ivf_route_scores / ivf_scan_topk / ivf_search — the optional cluster-routed
   (IVF) search: centroid scoring, then a gather scan of the probed inverted
   lists plus the rows appended since the index was built (approximate; the
-  exact search stays the default).
+  exact search stays the default). Two scans share one contract: the
+  per-query kernel (one block per query, list and slice) and, with
+  ``batched=True`` or from IVF_BATCHED_MIN_B queries on, the list-major one
+  (ivf_group_probes sorts the (query, probe) pairs by list;
+  ivf_scan_grouped_kernel gathers each probed list once per tile of 16
+  queries and scores the tile with MFMA).
 
 Policy: on a CUDA(ROCm) device the HIP extension is REQUIRED — ops raise
 if it is missing rather than silently falling back to eager PyTorch. The
@@ -397,6 +402,89 @@ def ivf_route_scores(queries: torch.Tensor, centroids: torch.Tensor) -> torch.Te
     return queries.float() @ centroids.float().t()
 
 
+#: queries per tile of the list-major scan (ivf_batch_plan.h IVF_BATCH_QTILE)
+IVF_BATCH_QTILE = 16
+
+#: batch size from which ``batched=None`` selects the list-major scan (None
+#: would mean never). Measured, profiles/routed_search.md "List-major scan":
+#: the smallest B from which it beats the per-query scan by more than the
+#: spread on both corpora at nprobe 32 and 64 (10M mixture: from 64 and 32,
+#: 200k encoder: from 128 and 64); never below 64
+IVF_BATCHED_MIN_B: Optional[int] = 128
+
+
+def ivf_batch_tile_bound(n_pairs: int, n_lists: int) -> int:
+    """Tiles that ``n_pairs`` (query, probe) pairs over ``n_lists`` lists and
+    the tail can make at most, whatever the grouping (mirror of
+    ivf_batch_plan.h ivf_batch_tile_bound)."""
+    return min(n_pairs, n_pairs // IVF_BATCH_QTILE + n_lists + 1)
+
+
+def ivf_group_probes(probes: torch.Tensor, n_lists: int):
+    """Group the (query, probe) pairs of a batch by list, for the list-major
+    scan. ``probes`` is integer [B, nprobe]; every query also probes the
+    tail, pseudo-list ``n_lists``, as its pair nprobe. Probes outside
+    [0, n_lists) are discarded. Returns
+
+    - ``pair_query``, ``pair_slot`` int32 [P], P = B * (nprobe + 1): the
+      query b and the probe rank y of each pair, sorted by list (discarded
+      pairs last);
+    - ``tiles`` int32 [3, T]: per tile its list, its first pair and its
+      pair count (1..IVF_BATCH_QTILE; 0 from the tile count on), T =
+      ``ivf_batch_tile_bound(P, n_lists)``. A tile never spans two lists;
+    - ``n_tiles`` int32 [1], on the probes' device.
+
+    Torch ops only, on any device, and none of them reads device memory on
+    the host: the launch is sized by the bound T. The extension runs the
+    same sequence (ivf_group_probes_op) inside ``ivf_scan_topk_batched``.
+    """
+    B, S = int(probes.shape[0]), int(probes.shape[1]) + 1
+    P, L, QT = B * S, int(n_lists), IVF_BATCH_QTILE
+    T = ivf_batch_tile_bound(P, L)
+    dev = probes.device
+    pl = probes.long()
+    pl = torch.where((pl >= 0) & (pl < L), pl, torch.full_like(pl, L + 1))
+    tail = torch.full((B, 1), L, dtype=torch.int64, device=dev)
+    keys = torch.cat([pl, tail], dim=1).reshape(P)
+    order = torch.sort(keys, stable=True).indices
+    counts = torch.zeros(L + 2, dtype=torch.int64, device=dev).scatter_add_(
+        0, keys, torch.ones(P, dtype=torch.int64, device=dev)
+    )[: L + 1]
+    starts = counts.cumsum(0) - counts
+    ntl = (counts + (QT - 1)) // QT
+    tend = ntl.cumsum(0)
+    n_tiles = tend[L : L + 1]
+    t = torch.arange(T, dtype=torch.int64, device=dev)
+    li = torch.searchsorted(tend, t, right=True).clamp_max(L)
+    within = t - (tend[li] - ntl[li])
+    live = t < n_tiles
+    zero = torch.zeros((), dtype=torch.int64, device=dev)
+    tfirst = torch.where(live, starts[li] + within * QT, zero)
+    tcnt = torch.where(live, (counts[li] - within * QT).clamp(0, QT), zero)
+    tiles = torch.stack([li, tfirst, tcnt]).to(torch.int32).contiguous()
+    return (
+        (order // S).to(torch.int32),
+        (order % S).to(torch.int32),
+        tiles,
+        n_tiles.to(torch.int32),
+    )
+
+
+#: widest row the list-major scan's LDS query tile holds (ivf_batch_plan.h
+#: IVF_BATCH_MAX_D); ``batched=None`` keeps wider rows on the per-query scan
+IVF_BATCH_MAX_D = 1472
+
+
+def _use_batched(batched: Optional[bool], B: int, D: int) -> bool:
+    if batched is None:
+        return (
+            IVF_BATCHED_MIN_B is not None
+            and B >= IVF_BATCHED_MIN_B
+            and D <= IVF_BATCH_MAX_D
+        )
+    return bool(batched)
+
+
 def ivf_scan_topk_ref(
     queries: torch.Tensor,
     segments,
@@ -443,6 +531,7 @@ def ivf_scan_topk(
     tail_lo: int,
     tail_hi: int,
     max_list_len: int = 0,
+    batched: Optional[bool] = None,
 ) -> Tuple[torch.Tensor, torch.Tensor]:
     """Exact top-k of each query over a candidate set given as inverted lists.
 
@@ -456,6 +545,13 @@ def ivf_scan_topk(
     padded with (-inf, -1) where the candidate set is shorter than k and
     past KMAX columns on GPU. ``max_list_len`` (the longest list, if known)
     only sizes the GPU grid.
+
+    ``batched`` picks the GPU scan: False the per-query kernel, True the
+    list-major one (each probed list gathered once per tile of
+    IVF_BATCH_QTILE queries, MFMA scoring; D <= IVF_BATCH_MAX_D), None the
+    list-major one from IVF_BATCHED_MIN_B queries on where D allows it. Both compute the same contract; scores may
+    differ by the fp32 summation order (<= D * 2^-22 for unit rows). On CPU
+    every value runs the reference.
     """
     if queries.device.type != "cuda":
         return ivf_scan_topk_ref(
@@ -464,7 +560,8 @@ def ivf_scan_topk(
     ext = _require_ext()
     dev = queries.device
     kk = min(int(k), KMAX)
-    scores, idx = ext.ivf_scan_topk(
+    scan = ext.ivf_scan_topk_batched if _use_batched(batched, queries.shape[0], queries.shape[1]) else ext.ivf_scan_topk
+    scores, idx = scan(
         queries,
         _segment_list(segments),
         offsets.to(device=dev, dtype=torch.int64).contiguous(),
@@ -511,13 +608,14 @@ def ivf_search(
     valid_n: int,
     n_indexed: int,
     max_list_len: int = 0,
+    batched: Optional[bool] = None,
 ) -> Tuple[torch.Tensor, torch.Tensor]:
     """Cluster-routed approximate top-k: score the L centroids, scan the
     ``nprobe`` best lists of each query plus the tail [n_indexed, valid_n)
     of rows appended since the index was built, return the exact top-k of
     that candidate set. With ``nprobe == L`` the candidate set is every row
-    and the result is the exact search's. Shapes and padding as
-    ``ivf_scan_topk``."""
+    and the result is the exact search's. Shapes, padding and
+    ``batched`` as ``ivf_scan_topk``."""
     L = int(centroids.shape[0])
     nprobe = max(1, min(int(nprobe), L))
     if queries.device.type != "cuda":
@@ -527,7 +625,8 @@ def ivf_search(
     ext = _require_ext()
     dev = queries.device
     kk = min(int(k), KMAX)
-    scores, idx = ext.ivf_search(
+    search = ext.ivf_search_batched if _use_batched(batched, queries.shape[0], queries.shape[1]) else ext.ivf_search
+    scores, idx = search(
         queries,
         _segment_list(segments),
         centroids,

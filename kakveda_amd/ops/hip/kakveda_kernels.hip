@@ -8,6 +8,7 @@
 #include <vector>
 #include "kernels_impl.h"
 #include "ivf_impl.h"
+#include "ivf_batch_impl.h"
 
 using namespace kakveda;
 
@@ -646,14 +647,19 @@ torch::Tensor ivf_route_scores_op(torch::Tensor queries, torch::Tensor centroids
   return out;
 }
 
-std::tuple<torch::Tensor, torch::Tensor> ivf_scan_topk(
-    torch::Tensor queries, std::vector<torch::Tensor> segments,
-    torch::Tensor offsets, torch::Tensor ids, torch::Tensor probes, int64_t k,
-    int64_t valid_n, int64_t tail_lo, int64_t tail_hi, int64_t max_list_len) {
-  // Exact top-k of each query over the rows of its probed lists plus the
-  // tail [tail_lo, tail_hi). max_list_len only sizes the grid (any value
-  // >= 0 gives the same result); rows short of k candidates come back padded
-  // with (NEG_INF, -1), which the Python op normalises.
+namespace {
+
+// What both routed scans check before anything is launched.
+struct IvfScanArgs {
+  IvfSegs segs;
+  int B, D, L, nprobe;
+};
+
+IvfScanArgs ivf_scan_args(const torch::Tensor& queries,
+                          const std::vector<torch::Tensor>& segments,
+                          const torch::Tensor& offsets, const torch::Tensor& ids,
+                          const torch::Tensor& probes, int64_t k, int64_t valid_n,
+                          int64_t tail_lo, int64_t tail_hi, int64_t max_list_len) {
   check_bf16_2d(queries, "queries");
   const int B = queries.size(0), D = queries.size(1);
   const IvfSegs segs = ivf_segs(segments, queries, (long)valid_n);
@@ -678,6 +684,23 @@ std::tuple<torch::Tensor, torch::Tensor> ivf_scan_topk(
   TORCH_CHECK(tail_lo >= 0 && tail_lo <= tail_hi && tail_hi <= valid_n,
               "tail range must satisfy 0 <= tail_lo <= tail_hi <= valid_n");
   TORCH_CHECK(max_list_len >= 0, "max_list_len must be >= 0");
+  return {segs, B, D, L, nprobe};
+}
+
+}  // namespace
+
+std::tuple<torch::Tensor, torch::Tensor> ivf_scan_topk(
+    torch::Tensor queries, std::vector<torch::Tensor> segments,
+    torch::Tensor offsets, torch::Tensor ids, torch::Tensor probes, int64_t k,
+    int64_t valid_n, int64_t tail_lo, int64_t tail_hi, int64_t max_list_len) {
+  // Exact top-k of each query over the rows of its probed lists plus the
+  // tail [tail_lo, tail_hi). max_list_len only sizes the grid (any value
+  // >= 0 gives the same result); rows short of k candidates come back padded
+  // with (NEG_INF, -1), which the Python op normalises.
+  const IvfScanArgs a = ivf_scan_args(queries, segments, offsets, ids, probes, k,
+                                      valid_n, tail_lo, tail_hi, max_list_len);
+  const IvfSegs& segs = a.segs;
+  const int B = a.B, D = a.D, L = a.L, nprobe = a.nprobe;
 
   auto dev = queries.device();
   auto stream = c10::hip::getCurrentHIPStream().stream();
@@ -737,6 +760,132 @@ std::tuple<torch::Tensor, torch::Tensor> ivf_search(
                        max_list_len);
 }
 
+// ---- list-major (batched) routed scan --------------------------------------
+
+std::vector<torch::Tensor> ivf_group_probes_op(torch::Tensor probes,
+                                               int64_t n_lists) {
+  // The B x (nprobe + 1) (query, probe) pairs - column nprobe being the tail,
+  // pseudo-list n_lists - sorted by list and cut into tiles of at most
+  // IVF_BATCH_QTILE pairs of one list; probes outside [0, n_lists) form a
+  // last group that gets no tile. Returns {pair_query i32 [P], pair_slot
+  // i32 [P], tiles i32 [3][T] (list, first pair, pair count; count 0 from
+  // the tile count on), n_tiles i32 [1]}, T = ivf_batch_tile_bound(P, L).
+  // Torch ops only, none of which reads device memory on the host (the
+  // same sequence as ops.ivf_group_probes in Python).
+  TORCH_CHECK(probes.dim() == 2 && probes.size(0) >= 1, "probes must be [B, nprobe]");
+  TORCH_CHECK(n_lists >= 0, "n_lists must be >= 0");
+  const int64_t B = probes.size(0), S = probes.size(1) + 1, P = B * S;
+  const int64_t L = n_lists, QT = IVF_BATCH_QTILE;
+  const int64_t T = ivf_batch_tile_bound(P, L);
+  auto i64 = torch::TensorOptions().dtype(torch::kInt64).device(probes.device());
+  auto pl = probes.to(torch::kInt64);
+  pl = torch::where((pl >= 0) & (pl < L), pl, torch::full({}, L + 1, i64));
+  auto keys = torch::cat({pl, torch::full({B, 1}, L, i64)}, 1).reshape({P});
+  auto order = std::get<1>(keys.sort(/*stable=*/true, /*dim=*/0, /*descending=*/false));
+  auto counts = torch::zeros({L + 2}, i64)
+                    .scatter_add_(0, keys, torch::ones({P}, i64))
+                    .slice(0, 0, L + 1);
+  auto starts = counts.cumsum(0) - counts;
+  auto ntl = (counts + (QT - 1)).floor_divide(QT);
+  auto tend = ntl.cumsum(0);
+  auto n_tiles = tend.slice(0, L, L + 1);
+  auto t = torch::arange(T, i64);
+  auto li = torch::searchsorted(tend, t, /*out_int32=*/false, /*right=*/true)
+                .clamp_max(L);
+  auto within = t - (tend.index_select(0, li) - ntl.index_select(0, li));
+  auto live = t < n_tiles;
+  auto zero = torch::zeros({}, i64);
+  auto tfirst = torch::where(live, starts.index_select(0, li) + within * QT, zero);
+  auto tcnt = torch::where(
+      live, (counts.index_select(0, li) - within * QT).clamp(0, QT), zero);
+  auto tiles = torch::stack({li, tfirst, tcnt}, 0).to(torch::kInt32).contiguous();
+  return {order.floor_divide(S).to(torch::kInt32).contiguous(),
+          order.remainder(S).to(torch::kInt32).contiguous(), tiles,
+          n_tiles.to(torch::kInt32).contiguous()};
+}
+
+std::tuple<torch::Tensor, torch::Tensor> ivf_scan_topk_batched(
+    torch::Tensor queries, std::vector<torch::Tensor> segments,
+    torch::Tensor offsets, torch::Tensor ids, torch::Tensor probes, int64_t k,
+    int64_t valid_n, int64_t tail_lo, int64_t tail_hi, int64_t max_list_len) {
+  // ivf_scan_topk's contract through the list-major kernel: group the
+  // (query, probe) pairs by list, scan every (tile, slice) once with
+  // ivf_scan_grouped_kernel, finish with emit_merge_topk.
+  const IvfScanArgs a = ivf_scan_args(queries, segments, offsets, ids, probes, k,
+                                      valid_n, tail_lo, tail_hi, max_list_len);
+  const int B = a.B, D = a.D, L = a.L, nprobe = a.nprobe;
+  const size_t lds = (size_t)ivf_batch_query_lds(D);
+  TORCH_CHECK(D <= IVF_BATCH_MAX_D, "D too large for the LDS query tile (at most ",
+              IVF_BATCH_MAX_D, ")");
+
+  auto dev = queries.device();
+  auto stream = c10::hip::getCurrentHIPStream().stream();
+  auto out_score = torch::empty(
+      {B, k}, torch::TensorOptions().dtype(torch::kFloat32).device(dev));
+  auto out_idx =
+      torch::empty({B, k}, torch::TensorOptions().dtype(torch::kInt64).device(dev));
+  const long tail_len = (long)(tail_hi - tail_lo);
+  // chunk the batch so that one launch's candidate buffer stays capped
+  const int chunk =
+      ivf_batch_chunk_queries((long)max_list_len, tail_len, nprobe, B, L);
+  for (int b0 = 0; b0 < B; b0 += chunk) {
+    const int nb = std::min(B - b0, chunk);
+    const IvfBatchPlan p =
+        plan_ivf_batch((long)max_list_len, tail_len, nprobe, nb, L);
+    auto grp = ivf_group_probes_op(probes.slice(0, b0, b0 + nb), L);
+    const int* tiles = grp[2].data_ptr<int>();
+    TORCH_CHECK(grp[2].size(1) == p.max_tiles, "tile table / plan mismatch");
+    // preset every slot to 0 (empty): blocks store only what they scanned
+    auto cand = torch::zeros(
+        {(long)nb, p.cand_entries},
+        torch::TensorOptions().dtype(torch::kInt64).device(dev));
+    auto ccount = torch::full(
+        {(long)nb}, (int64_t)p.cand_entries,
+        torch::TensorOptions().dtype(torch::kInt32).device(dev));
+    // grid.y holds at most 65535 tiles
+    for (long t0 = 0; t0 < p.max_tiles; t0 += 65535) {
+      const int nt = (int)std::min(p.max_tiles - t0, 65535L);
+      hipLaunchKernelGGL(
+          ivf_scan_grouped_kernel, dim3(p.slices, nt), dim3(256), lds, stream,
+          (const bf16_t*)queries.data_ptr() + (size_t)b0 * D, a.segs,
+          (const long*)offsets.data_ptr<int64_t>(), ids.data_ptr<int>(),
+          grp[0].data_ptr<int>(), grp[1].data_ptr<int>(), tiles,
+          tiles + p.max_tiles, tiles + 2 * p.max_tiles, grp[3].data_ptr<int>(),
+          (int)t0, nb, nprobe + 1, L, (long)ids.size(0), D, (long)valid_n,
+          (long)tail_lo, (long)tail_hi, p.pairs,
+          (unsigned long long*)cand.data_ptr<int64_t>());
+    }
+    hipLaunchKernelGGL(emit_merge_topk, dim3(nb), dim3(256), 0, stream,
+                       (const unsigned long long*)cand.data_ptr<int64_t>(),
+                       (const unsigned*)ccount.data_ptr<int>(),
+                       out_score.data_ptr<float>() + (size_t)b0 * k,
+                       (long*)out_idx.data_ptr<int64_t>() + (size_t)b0 * k, nb,
+                       p.cand_entries, (int)k);
+  }
+  return {out_score, out_idx};
+}
+
+std::tuple<torch::Tensor, torch::Tensor> ivf_search_batched(
+    torch::Tensor queries, std::vector<torch::Tensor> segments,
+    torch::Tensor centroids, torch::Tensor offsets, torch::Tensor ids,
+    int64_t nprobe, int64_t k, int64_t valid_n, int64_t n_indexed,
+    int64_t max_list_len) {
+  // ivf_search with the list-major scan: route -> select -> group -> scan
+  // -> merge (the last three inside ivf_scan_topk_batched).
+  TORCH_CHECK(offsets.dim() == 1 && offsets.size(0) == centroids.size(0) + 1,
+              "offsets must have L+1 entries for L centroids");
+  TORCH_CHECK(ids.dim() == 1 && ids.size(0) == n_indexed,
+              "ids must have n_indexed entries");
+  TORCH_CHECK(n_indexed >= 0, "n_indexed must be >= 0");
+  const int64_t L = centroids.size(0);
+  TORCH_CHECK(nprobe >= 1 && nprobe <= L, "nprobe must be in [1, n_lists]");
+  auto scores = ivf_route_scores_op(queries, centroids);
+  auto probes = std::get<1>(scores.topk(nprobe, 1)).to(torch::kInt32).contiguous();
+  return ivf_scan_topk_batched(queries, std::move(segments), offsets, ids, probes,
+                               k, valid_n, std::min(n_indexed, valid_n), valid_n,
+                               max_list_len);
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("cosine_topk", &cosine_topk, "fused cosine top-k (MFMA + LDS top-k)");
   m.def("cosine_topk_filtered", &cosine_topk_filtered,
@@ -768,7 +917,25 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("ids"), pybind11::arg("nprobe"), pybind11::arg("k"),
         pybind11::arg("valid_n"), pybind11::arg("n_indexed"),
         pybind11::arg("max_list_len") = (int64_t)0);
+  m.def("ivf_group_probes", &ivf_group_probes_op,
+        "group (query, probe) pairs by list into tiles of IVF_BATCH_QTILE",
+        pybind11::arg("probes"), pybind11::arg("n_lists"));
+  m.def("ivf_scan_topk_batched", &ivf_scan_topk_batched,
+        "ivf_scan_topk through the list-major MFMA scan",
+        pybind11::arg("queries"), pybind11::arg("segments"),
+        pybind11::arg("offsets"), pybind11::arg("ids"), pybind11::arg("probes"),
+        pybind11::arg("k"), pybind11::arg("valid_n"), pybind11::arg("tail_lo"),
+        pybind11::arg("tail_hi"), pybind11::arg("max_list_len") = (int64_t)0);
+  m.def("ivf_search_batched", &ivf_search_batched,
+        "cluster-routed (IVF) top-k search through the list-major MFMA scan",
+        pybind11::arg("queries"), pybind11::arg("segments"),
+        pybind11::arg("centroids"), pybind11::arg("offsets"),
+        pybind11::arg("ids"), pybind11::arg("nprobe"), pybind11::arg("k"),
+        pybind11::arg("valid_n"), pybind11::arg("n_indexed"),
+        pybind11::arg("max_list_len") = (int64_t)0);
   m.attr("KMAX") = KMAX;
+  m.attr("IVF_BATCH_QTILE") = IVF_BATCH_QTILE;
+  m.attr("IVF_BATCH_MAX_D") = IVF_BATCH_MAX_D;
   // the widest row the C<=64 assignment kernel can keep resident in LDS
   m.attr("KMEANS_ASSIGN_MAX_D") = kmeans_assign_max_d();
 }

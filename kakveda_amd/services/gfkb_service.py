@@ -94,7 +94,11 @@ class MatchBatcher:
                 first = [b["first"] for b in batch]
                 # an all-unset batch makes the call it always made
                 extra = {"filter_first": first} if any(first) else {}
-                # one request asking for exact makes its whole batch exact
+                # one request asking for exact makes its whole batch exact.
+                # A routed batch needs no cap on its size: from
+                # ops.IVF_BATCHED_MIN_B queries on the store takes the
+                # list-major scan, which gathers a probed list once per 16
+                # queries and stays below the exact search's time
                 if any(b["exact"] for b in batch):
                     extra["nprobe"] = 0
                 results = self.engine.match_batch(
