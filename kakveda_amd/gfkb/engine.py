@@ -75,7 +75,10 @@ class EmbeddingStore:
     (gfkb/ivf.py) and ``search(..., nprobe=n)`` then scans only the n best
     inverted lists per query plus the tail of rows appended since the build.
     It is approximate and strictly opt-in: ``nprobe=None`` is the exact
-    search, whether an index is attached or not.
+    search, whether an index is attached or not. A label-filtered batch is
+    routed only with ``route_filtered=True`` (``ops.ivf_search_filtered``);
+    the per-label row counts kept at insertion then let the store re-run,
+    exactly, the queries whose label's rows sat in unprobed lists.
     """
 
     def __init__(
@@ -97,13 +100,32 @@ class EmbeddingStore:
             torch.zeros(capacity, dim, dtype=self.dtype, device=self.device)
         ]
         self._labels: List[torch.Tensor] = [self._new_labels(capacity)]
+        #: rows per label, kept on the host by append/adopt (the insert
+        #: path) for the exact fill of a routed filtered search
+        self._label_counts: Dict[int, int] = {}
         self.count = 0
         #: the routed-search index (None: exact search only)
         self.index = None
         self._stale_warned = False
+        #: filtered queries a routed filtered search handed to the exact fill
+        self.exact_fills = 0
 
     def _new_labels(self, n: int) -> torch.Tensor:
         return torch.full((n,), -1, dtype=torch.int32, device=self.device)
+
+    def _count_labels(self, labels: Optional[torch.Tensor], n: int) -> None:
+        """Add ``n`` new rows to the per-label row counts (None: all -1)."""
+        if labels is None:
+            if n:
+                self._label_counts[-1] = self._label_counts.get(-1, 0) + n
+            return
+        values, counts = torch.unique(labels, return_counts=True)
+        for v, c in zip(values.tolist(), counts.tolist()):
+            self._label_counts[int(v)] = self._label_counts.get(int(v), 0) + int(c)
+
+    def label_rows(self, label: int) -> int:
+        """Rows that carry ``label`` (counted at insertion, on the host)."""
+        return self._label_counts.get(int(label), 0)
 
     @property
     def capacity(self) -> int:
@@ -151,6 +173,8 @@ class EmbeddingStore:
         self._segments = [data]
         self._labels = [lab]
         self.count = n
+        self._label_counts = {}
+        self._count_labels(labels, n)
         self.index = None  # it described the rows just replaced
 
     def append(self, rows: torch.Tensor, labels: Optional[torch.Tensor] = None) -> int:
@@ -159,6 +183,10 @@ class EmbeddingStore:
         n = rows.shape[0]
         if labels is not None:
             assert labels.shape == (n,)
+        # counted where the caller's labels live (host tensors from the
+        # engine): no device read on the insert path
+        self._count_labels(labels, n)
+        if labels is not None:
             labels = labels.to(device=self.device, dtype=torch.int32)
         self._grow_to(self.count + n)
         first = self.count
@@ -220,10 +248,7 @@ class EmbeddingStore:
             return 0.0
         return max(self.count - index.n_indexed, 0) / float(index.n_indexed)
 
-    def _search_routed(
-        self, q: torch.Tensor, k: int, count: int, nprobe: int, index,
-        batched: Optional[bool] = None,
-    ) -> Tuple[torch.Tensor, torch.Tensor]:
+    def _warn_stale(self, index) -> None:
         tail = self.count - index.n_indexed
         if not self._stale_warned and tail > STALE_WARN_FRACTION * index.n_indexed:
             self._stale_warned = True
@@ -235,6 +260,12 @@ class EmbeddingStore:
                 index.n_indexed,
                 100.0 * tail / max(index.n_indexed, 1),
             )
+
+    def _search_routed(
+        self, q: torch.Tensor, k: int, count: int, nprobe: int, index,
+        batched: Optional[bool] = None,
+    ) -> Tuple[torch.Tensor, torch.Tensor]:
+        self._warn_stale(index)
         # a snapshot older than the index is safe: the scan drops listed ids
         # >= count and the tail is then empty
         return ops.ivf_search(
@@ -251,6 +282,62 @@ class EmbeddingStore:
             batched=batched,
         )
 
+    def _search_routed_filtered(
+        self, q: torch.Tensor, k: int, count: int, want: torch.Tensor,
+        nprobe: int, index, batched: Optional[bool], fill_exact: bool,
+    ) -> Tuple[torch.Tensor, torch.Tensor]:
+        """The routed search with the label predicate inside the scan, then
+        the exact fill: a filtered query that holds fewer live results than
+        ``min(k, rows of its label)`` had rows of its label in lists it did
+        not probe, and is answered again by the exact filtered search."""
+        self._warn_stale(index)
+        segs = self._live_segments(count)
+        w = want.to(device=self.device, dtype=torch.int32)
+        nprobe = min(nprobe, index.n_lists)
+        want_h = want.tolist()
+        if (
+            batched is None
+            and len(want_h) < ops.IVF_FILTERED_SPARSE_MIN_B
+            and all(wb >= 0 for wb in want_h)
+            and max(self.label_rows(wb) for wb in want_h)
+            <= ops.IVF_FILTERED_SPARSE_SHARE * count
+        ):
+            # every query wants a rare label: the per-query scan skips
+            # nearly every row and stays ahead up to that many queries
+            batched = False
+        scores, idx = ops.ivf_search_filtered(
+            q,
+            [seg for seg, _v, _b in segs],
+            self._labels[: len(segs)],  # the live segments are a prefix
+            w,
+            index.centroids,
+            index.offsets,
+            index.ids,
+            nprobe,
+            k,
+            count,
+            index.n_indexed,
+            index.max_list_len,
+            batched=batched,
+        )
+        if not fill_exact or nprobe >= index.n_lists:
+            return scores, idx
+        # the counts may include rows appended after the ``count`` snapshot:
+        # that can only ask for an exact re-run that was not needed
+        found = (idx >= 0).sum(dim=1).tolist()
+        short = [
+            b
+            for b, wb in enumerate(want_h)
+            if wb >= 0 and found[b] < min(k, self.label_rows(wb))
+        ]
+        self.exact_fills += len(short)
+        if short:
+            sel = torch.tensor(short, dtype=torch.int64, device=self.device)
+            fill_s, fill_i = self.search(q[sel], k, valid_n=count, want=w[sel])
+            scores[sel] = fill_s
+            idx[sel] = fill_i
+        return scores, idx
+
     def search(
         self,
         queries: torch.Tensor,
@@ -260,6 +347,8 @@ class EmbeddingStore:
         nprobe: Optional[int] = None,
         index=None,
         batched: Optional[bool] = None,
+        route_filtered: bool = False,
+        fill_exact: bool = True,
     ) -> Tuple[torch.Tensor, torch.Tensor]:
         """Top-k over the first ``valid_n`` rows (default: the live count).
         Passing a snapshot of ``count`` makes the search safe to run
@@ -276,7 +365,19 @@ class EmbeddingStore:
         list count) plus every row appended since the build. It raises
         without an index. A label-filtered batch (``want`` set) is answered
         by the exact filtered search whatever ``nprobe`` says: exact is
-        never worse, and a filtered query is not silently routed. ``index``
+        never worse, and a filtered query is not silently routed - unless
+        ``route_filtered`` is set: then the batch runs the routed search
+        with the label predicate inside the scan
+        (``ops.ivf_search_filtered``; queries with a negative ``want`` ride
+        along unfiltered). With ``fill_exact`` (the default) every filtered
+        query that then holds fewer than ``min(k, rows of its label)`` live
+        results is run again through the exact filtered search, so a label
+        with at least k rows never comes back short because its rows sat in
+        unprobed lists; ``fill_exact=False`` returns the routed answer as it
+        is. With ``batched=None`` a batch whose every query wants a label
+        that at most ``ops.IVF_FILTERED_SPARSE_SHARE`` of the rows carry
+        stays on the per-query scan below ``ops.IVF_FILTERED_SPARSE_MIN_B``
+        queries (measured: it skips nearly every row there). ``index``
         is the index to route through (default: the attached one), for
         callers that snapshot it together with ``valid_n``. ``batched``
         picks the routed scan kernel (``ops.ivf_scan_topk``: None chooses by
@@ -294,6 +395,10 @@ class EmbeddingStore:
                 )
             if want is None and count > 0:
                 return self._search_routed(q, k, count, int(nprobe), index, batched)
+            if route_filtered and count > 0:
+                return self._search_routed_filtered(
+                    q, k, count, want, int(nprobe), index, batched, fill_exact
+                )
         segs = self._live_segments(count)
         w = None if want is None else want.to(device=self.device, dtype=torch.int32)
 
@@ -441,6 +546,7 @@ class GfkbEngine:
         encoder_seed: int = 1234,
         top_k: int = 5,
         nprobe: Optional[int] = None,
+        route_filtered: bool = False,
     ):
         self.data_dir = Path(data_dir)
         self.data_dir.mkdir(parents=True, exist_ok=True)
@@ -450,6 +556,10 @@ class GfkbEngine:
         #: default routed-search width of match()/match_batch(); None or 0
         #: is the exact search. Only takes effect once an index is built.
         self.nprobe = nprobe
+        #: whether a batch with a filter-first query stays on the routed
+        #: search (label predicate in the scan, exact fill) when ``nprobe``
+        #: and an index are in effect; False: such a batch runs exact
+        self.route_filtered = route_filtered
         self._lock = threading.RLock()
 
         self.encoder = TraceEncoder(dim=dim, hash_dim=hash_dim, seed=encoder_seed, device=device)
@@ -611,18 +721,20 @@ class GfkbEngine:
         top_k: Optional[int] = None,
         filter_first: bool = False,
         nprobe: Optional[int] = None,
+        route_filtered: Optional[bool] = None,
     ) -> List[FailureMatch]:
         """Top-k failures by cosine similarity, then optional type filter
         (reference order: cut to top-k first, filter second). With
         ``filter_first`` the type filter runs inside the search instead:
-        the top-k of the failures of that type. ``nprobe``: see
-        ``match_batch``."""
+        the top-k of the failures of that type. ``nprobe`` and
+        ``route_filtered``: see ``match_batch``."""
         return self.match_batch(
             [signature_text],
             failure_types=[failure_type],
             top_k=top_k,
             filter_first=filter_first,
             nprobe=nprobe,
+            route_filtered=route_filtered,
         )[0]
 
     def match_batch(
@@ -632,6 +744,7 @@ class GfkbEngine:
         top_k: Optional[int] = None,
         filter_first: Union[bool, Sequence[bool]] = False,
         nprobe: Optional[int] = None,
+        route_filtered: Optional[bool] = None,
     ) -> List[List[FailureMatch]]:
         """Match a whole batch of signatures with ONE fused-kernel launch.
 
@@ -657,6 +770,12 @@ class GfkbEngine:
         default is ignored (an explicit ``nprobe`` raises); a batch with a
         filter-first query runs the exact filtered search; sharded and
         distributed stores refuse an explicit ``nprobe``.
+
+        ``route_filtered`` (default: the engine's) keeps such a batch routed
+        instead, when an ``nprobe`` and an index are in effect: one routed
+        search with the type filter inside the scan, the batch's other
+        queries riding along unfiltered, and the store's exact fill for any
+        filtered query whose type's rows sat in lists it did not probe.
         """
         nq = len(signature_texts)
         k = top_k or self.top_k
@@ -702,6 +821,7 @@ class GfkbEngine:
             probe = self.nprobe if index is not None else None
         else:
             probe = nprobe
+        route_f = self.route_filtered if route_filtered is None else bool(route_filtered)
         # unknown types cannot match: search only the other queries
         live = [r for r in range(nq) if not unknown[r]]
         if not live:
@@ -711,7 +831,13 @@ class GfkbEngine:
             want_t = torch.tensor(
                 [-1 if want[r] is None else want[r] for r in live], dtype=torch.int32
             )
-            scores, idx = store.search(q, min(k, valid), valid_n=valid, want=want_t)
+            if route_f and probe and index is not None:
+                scores, idx = store.search(
+                    q, min(k, valid), valid_n=valid, want=want_t, nprobe=probe,
+                    index=index, route_filtered=True,
+                )
+            else:
+                scores, idx = store.search(q, min(k, valid), valid_n=valid, want=want_t)
         elif probe:
             scores, idx = store.search(
                 q, min(k, valid), valid_n=valid, nprobe=probe, index=index

@@ -24,6 +24,10 @@ Kernels (kakveda_amd/ops/hip/):
   (ivf_group_probes sorts the (query, probe) pairs by list;
   ivf_scan_grouped_kernel gathers each probed list once per tile of 16
   queries and scores the tile with MFMA).
+- ivf_scan_topk_filtered / ivf_search_filtered — the routed search with the
+  label predicate of cosine_topk_filtered inside either scan (sibling
+  kernels; the unfiltered ones are untouched), so a filter-first request
+  can stay routed.
 
 Policy: on a CUDA(ROCm) device the HIP extension is REQUIRED — ops raise
 if it is missing rather than silently falling back to eager PyTorch. The
@@ -629,6 +633,215 @@ def ivf_search(
     scores, idx = search(
         queries,
         _segment_list(segments),
+        centroids,
+        offsets.to(device=dev, dtype=torch.int64).contiguous(),
+        ids.to(device=dev, dtype=torch.int32).contiguous(),
+        nprobe,
+        kk,
+        int(valid_n),
+        int(n_indexed),
+        int(max_list_len),
+    )
+    scores = torch.where(idx < 0, torch.full_like(scores, float("-inf")), scores)
+    return _pad_topk(scores, idx, k)
+
+
+# ---------------------------------------------------------------------------
+# label-filtered routed search
+# ---------------------------------------------------------------------------
+
+#: a batch whose every query is filtered to a label that at most this share
+#: of the rows carry is "sparse": the per-query scan skips almost every row
+#: (no load, no multiply) while the list-major scan still gathers them all,
+#: so the crossover moves. Measured, profiles/routed_filtered.md "Crossover":
+#: at 1% and 0.1% the list-major scan wins only from 1024 queries on (at 512
+#: the per-query scan is 15% / 31% faster, spread <= 4.7%), against 128 at
+#: 50%. Only a caller that knows the labels' row counts can apply it
+#: (``EmbeddingStore.search``); the ops themselves go by IVF_BATCHED_MIN_B.
+IVF_FILTERED_SPARSE_SHARE = 0.01
+IVF_FILTERED_SPARSE_MIN_B = 1024
+
+
+def _label_list(labels, segments: list) -> list:
+    """``labels`` as one tensor per segment: a list is taken as it is, one
+    tensor is split at the segment boundaries."""
+    if not isinstance(labels, torch.Tensor):
+        return list(labels)
+    if len(segments) == 1:
+        return [labels]
+    return list(torch.split(labels, [int(s.shape[0]) for s in segments]))
+
+
+def ivf_scan_topk_filtered_ref(
+    queries: torch.Tensor,
+    segments,
+    labels,
+    want: torch.Tensor,
+    offsets: torch.Tensor,
+    ids: torch.Tensor,
+    probes: torch.Tensor,
+    k: int,
+    valid_n: int,
+    tail_lo: int,
+    tail_hi: int,
+) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Plain-PyTorch reference of ``ivf_scan_topk_filtered`` (fp32
+    accumulate): ``ivf_scan_topk_ref`` over the candidates whose label the
+    query wants."""
+    segs = _segment_list(segments)
+    dev = queries.device
+    B = queries.shape[0]
+    L = int(offsets.shape[0]) - 1
+    off = offsets.to("cpu").long().tolist()
+    ids_l = ids.to(dev).long()
+    lab = torch.cat([l.to(dev).long().reshape(-1) for l in _label_list(labels, segs)])
+    w = want.to("cpu").long().tolist()
+    tail = torch.arange(int(tail_lo), int(tail_hi), dtype=torch.int64, device=dev)
+    out_s = torch.full((B, k), float("-inf"), dtype=torch.float32, device=dev)
+    out_i = torch.full((B, k), -1, dtype=torch.int64, device=dev)
+    for b, row in enumerate(probes.to("cpu").long().tolist()):
+        parts = [ids_l[off[l] : off[l + 1]] for l in row if 0 <= l < L]
+        rows = torch.cat(parts + [tail])
+        rows = rows[(rows >= 0) & (rows < int(valid_n))]
+        if w[b] >= 0:
+            rows = rows[lab[rows] == w[b]]
+        if rows.numel() == 0:
+            continue
+        sims = _gather_rows(segs, rows).float() @ queries[b].float()
+        kk = min(k, int(rows.numel()))
+        s, sel = torch.topk(sims, kk)
+        out_s[b, :kk] = s
+        out_i[b, :kk] = rows[sel]
+    return out_s, out_i
+
+
+def ivf_scan_topk_filtered(
+    queries: torch.Tensor,
+    segments,
+    labels,
+    want: torch.Tensor,
+    offsets: torch.Tensor,
+    ids: torch.Tensor,
+    probes: torch.Tensor,
+    k: int,
+    valid_n: int,
+    tail_lo: int,
+    tail_hi: int,
+    max_list_len: int = 0,
+    batched: Optional[bool] = None,
+) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``ivf_scan_topk`` with a per-query label predicate pushed into the scan.
+
+    labels: int32, one per store row (-1 = unlabelled), as one tensor or as
+    one tensor per segment; want: int32 [B]. A candidate row r is eligible
+    for query b iff ``want[b] < 0 or label(r) == want[b]`` (the rule of
+    ``cosine_topk_filtered``), so a batch may mix filtered and unfiltered
+    queries in one launch. An ineligible row is treated as a row id outside
+    [0, valid_n) is: never inserted (and, in the per-query scan, not read
+    from memory; the list-major scan scores a row for its whole tile of
+    queries and filters at the insert). Everything else -
+    shapes, the (-inf, -1) padding, the KMAX clamp, ``max_list_len`` and
+    ``batched`` - is as ``ivf_scan_topk``; with ``want < 0`` everywhere the
+    result is that op's.
+    """
+    if queries.device.type != "cuda":
+        return ivf_scan_topk_filtered_ref(
+            queries, segments, labels, want, offsets, ids, probes, k, valid_n,
+            tail_lo, tail_hi,
+        )
+    ext = _require_ext()
+    dev = queries.device
+    kk = min(int(k), KMAX)
+    segs = _segment_list(segments)
+    scan = (
+        ext.ivf_scan_topk_batched_filtered
+        if _use_batched(batched, queries.shape[0], queries.shape[1])
+        else ext.ivf_scan_topk_filtered
+    )
+    scores, idx = scan(
+        queries,
+        segs,
+        [l.to(device=dev, dtype=torch.int32).contiguous() for l in _label_list(labels, segs)],
+        want.to(device=dev, dtype=torch.int32).contiguous(),
+        offsets.to(device=dev, dtype=torch.int64).contiguous(),
+        ids.to(device=dev, dtype=torch.int32).contiguous(),
+        probes.to(device=dev, dtype=torch.int32).contiguous(),
+        kk,
+        int(valid_n),
+        int(tail_lo),
+        int(tail_hi),
+        int(max_list_len),
+    )
+    scores = torch.where(idx < 0, torch.full_like(scores, float("-inf")), scores)
+    return _pad_topk(scores, idx, k)
+
+
+def ivf_search_filtered_ref(
+    queries: torch.Tensor,
+    segments,
+    labels,
+    want: torch.Tensor,
+    centroids: torch.Tensor,
+    offsets: torch.Tensor,
+    ids: torch.Tensor,
+    nprobe: int,
+    k: int,
+    valid_n: int,
+    n_indexed: int,
+) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Plain-PyTorch reference of ``ivf_search_filtered`` (fp32 accumulate)."""
+    route = queries.float() @ centroids.float().t()
+    probes = torch.topk(route, min(int(nprobe), route.shape[1]), dim=1).indices
+    return ivf_scan_topk_filtered_ref(
+        queries, segments, labels, want, offsets, ids, probes, k, valid_n,
+        min(int(n_indexed), int(valid_n)), valid_n,
+    )
+
+
+def ivf_search_filtered(
+    queries: torch.Tensor,
+    segments,
+    labels,
+    want: torch.Tensor,
+    centroids: torch.Tensor,
+    offsets: torch.Tensor,
+    ids: torch.Tensor,
+    nprobe: int,
+    k: int,
+    valid_n: int,
+    n_indexed: int,
+    max_list_len: int = 0,
+    batched: Optional[bool] = None,
+) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``ivf_search`` restricted per query to the rows of one label: route on
+    the centroids as the unfiltered search does (the lists know nothing of
+    labels), scan the ``nprobe`` best lists plus the tail, and return the
+    top-k of the eligible rows among them. ``labels`` and ``want`` as
+    ``ivf_scan_topk_filtered``. A query comes back short of k when its
+    label's rows sit in lists it did not probe; ``EmbeddingStore.search``
+    fills such rows from the exact filtered search. With ``nprobe == L`` the
+    result is ``cosine_topk_filtered``'s."""
+    L = int(centroids.shape[0])
+    nprobe = max(1, min(int(nprobe), L))
+    if queries.device.type != "cuda":
+        return ivf_search_filtered_ref(
+            queries, segments, labels, want, centroids, offsets, ids, nprobe, k,
+            valid_n, n_indexed,
+        )
+    ext = _require_ext()
+    dev = queries.device
+    kk = min(int(k), KMAX)
+    segs = _segment_list(segments)
+    search = (
+        ext.ivf_search_batched_filtered
+        if _use_batched(batched, queries.shape[0], queries.shape[1])
+        else ext.ivf_search_filtered
+    )
+    scores, idx = search(
+        queries,
+        segs,
+        [l.to(device=dev, dtype=torch.int32).contiguous() for l in _label_list(labels, segs)],
+        want.to(device=dev, dtype=torch.int32).contiguous(),
         centroids,
         offsets.to(device=dev, dtype=torch.int64).contiguous(),
         ids.to(device=dev, dtype=torch.int32).contiguous(),

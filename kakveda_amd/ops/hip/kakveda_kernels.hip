@@ -687,16 +687,51 @@ IvfScanArgs ivf_scan_args(const torch::Tensor& queries,
   return {segs, B, D, L, nprobe};
 }
 
-}  // namespace
+// The label predicate of a filtered routed launch: the by-value table of
+// per-segment label pointers and the per-query wants. Refuses, before
+// anything is launched, labels the kernels' row -> segment function would
+// address out of bounds.
+struct IvfFilter {
+  IvfLabels labels;
+  const int* want;
+};
 
-std::tuple<torch::Tensor, torch::Tensor> ivf_scan_topk(
-    torch::Tensor queries, std::vector<torch::Tensor> segments,
-    torch::Tensor offsets, torch::Tensor ids, torch::Tensor probes, int64_t k,
-    int64_t valid_n, int64_t tail_lo, int64_t tail_hi, int64_t max_list_len) {
-  // Exact top-k of each query over the rows of its probed lists plus the
-  // tail [tail_lo, tail_hi). max_list_len only sizes the grid (any value
-  // >= 0 gives the same result); rows short of k candidates come back padded
-  // with (NEG_INF, -1), which the Python op normalises.
+IvfFilter ivf_filter(const std::vector<torch::Tensor>& segments,
+                     const std::vector<torch::Tensor>& labels,
+                     const torch::Tensor& want, const torch::Tensor& queries) {
+  TORCH_CHECK(labels.size() == segments.size(), "labels needs one tensor per segment (",
+              segments.size(), "), got ", labels.size());
+  TORCH_CHECK(!segments.empty() && segments.size() <= (size_t)IVF_MAX_SEGMENTS,
+              "routed search supports 1 to ", IVF_MAX_SEGMENTS, " store segments");
+  IvfFilter f{};
+  const int n = (int)labels.size();
+  for (int i = 0; i < n; ++i) {
+    check_i32_gpu(labels[i], 1, "labels");
+    TORCH_CHECK(labels[i].device() == queries.device(),
+                "labels and queries must be on one device");
+    TORCH_CHECK(segments[i].dim() == 2 && labels[i].size(0) == segments[i].size(0),
+                "labels of segment ", i, " must have exactly its ",
+                segments[i].dim() == 2 ? segments[i].size(0) : -1, " rows, got ",
+                labels[i].size(0));
+    f.labels.base[i] = labels[i].data_ptr<int>();
+  }
+  for (int i = n; i < IVF_MAX_SEGMENTS; ++i) f.labels.base[i] = f.labels.base[0];
+  check_i32_gpu(want, 1, "want");
+  TORCH_CHECK(want.device() == queries.device(),
+              "want and queries must be on one device");
+  TORCH_CHECK(queries.dim() == 2 && want.size(0) == queries.size(0),
+              "want needs one entry per query");
+  f.want = want.data_ptr<int>();
+  return f;
+}
+
+// ivf_scan_topk, and with a filter ivf_scan_topk_filtered: the same plan,
+// candidate buffer and merge; only the scan kernel differs.
+std::tuple<torch::Tensor, torch::Tensor> ivf_scan_topk_impl(
+    const torch::Tensor& queries, const std::vector<torch::Tensor>& segments,
+    const torch::Tensor& offsets, const torch::Tensor& ids,
+    const torch::Tensor& probes, int64_t k, int64_t valid_n, int64_t tail_lo,
+    int64_t tail_hi, int64_t max_list_len, const IvfFilter* filter) {
   const IvfScanArgs a = ivf_scan_args(queries, segments, offsets, ids, probes, k,
                                       valid_n, tail_lo, tail_hi, max_list_len);
   const IvfSegs& segs = a.segs;
@@ -719,13 +754,23 @@ std::tuple<torch::Tensor, torch::Tensor> ivf_scan_topk(
     auto ccount = torch::full(
         {(long)nb}, (int64_t)p.cand_entries,
         torch::TensorOptions().dtype(torch::kInt32).device(dev));
-    hipLaunchKernelGGL(
-        ivf_scan_topk_kernel, dim3(p.slices, p.sources, nb), dim3(256),
-        (size_t)D * 2, stream, (const bf16_t*)queries.data_ptr() + (size_t)b0 * D,
-        segs, (const long*)offsets.data_ptr<int64_t>(), ids.data_ptr<int>(),
-        probes.data_ptr<int>() + (size_t)b0 * nprobe, nprobe, L,
-        (long)ids.size(0), D, (long)valid_n, (long)tail_lo, (long)tail_hi,
-        (unsigned long long*)cand.data_ptr<int64_t>());
+    if (filter)
+      hipLaunchKernelGGL(
+          ivf_scan_topk_filtered_kernel, dim3(p.slices, p.sources, nb), dim3(256),
+          (size_t)D * 2, stream, (const bf16_t*)queries.data_ptr() + (size_t)b0 * D,
+          segs, filter->labels, filter->want + b0,
+          (const long*)offsets.data_ptr<int64_t>(), ids.data_ptr<int>(),
+          probes.data_ptr<int>() + (size_t)b0 * nprobe, nprobe, L,
+          (long)ids.size(0), D, (long)valid_n, (long)tail_lo, (long)tail_hi,
+          (unsigned long long*)cand.data_ptr<int64_t>());
+    else
+      hipLaunchKernelGGL(
+          ivf_scan_topk_kernel, dim3(p.slices, p.sources, nb), dim3(256),
+          (size_t)D * 2, stream, (const bf16_t*)queries.data_ptr() + (size_t)b0 * D,
+          segs, (const long*)offsets.data_ptr<int64_t>(), ids.data_ptr<int>(),
+          probes.data_ptr<int>() + (size_t)b0 * nprobe, nprobe, L,
+          (long)ids.size(0), D, (long)valid_n, (long)tail_lo, (long)tail_hi,
+          (unsigned long long*)cand.data_ptr<int64_t>());
     hipLaunchKernelGGL(emit_merge_topk, dim3(nb), dim3(256), 0, stream,
                        (const unsigned long long*)cand.data_ptr<int64_t>(),
                        (const unsigned*)ccount.data_ptr<int>(),
@@ -734,6 +779,50 @@ std::tuple<torch::Tensor, torch::Tensor> ivf_scan_topk(
                        p.cand_entries, (int)k);
   }
   return {out_score, out_idx};
+}
+
+// route -> select: score the centroids and take the nprobe best lists per
+// query (torch.topk on the tiny [B, L] score tensor).
+torch::Tensor ivf_route_probes(const torch::Tensor& queries,
+                               const torch::Tensor& centroids,
+                               const torch::Tensor& offsets,
+                               const torch::Tensor& ids, int64_t nprobe,
+                               int64_t n_indexed) {
+  TORCH_CHECK(offsets.dim() == 1 && offsets.size(0) == centroids.size(0) + 1,
+              "offsets must have L+1 entries for L centroids");
+  TORCH_CHECK(ids.dim() == 1 && ids.size(0) == n_indexed,
+              "ids must have n_indexed entries");
+  TORCH_CHECK(n_indexed >= 0, "n_indexed must be >= 0");
+  const int64_t L = centroids.size(0);
+  TORCH_CHECK(nprobe >= 1 && nprobe <= L, "nprobe must be in [1, n_lists]");
+  auto scores = ivf_route_scores_op(queries, centroids);
+  return std::get<1>(scores.topk(nprobe, 1)).to(torch::kInt32).contiguous();
+}
+
+}  // namespace
+
+std::tuple<torch::Tensor, torch::Tensor> ivf_scan_topk(
+    torch::Tensor queries, std::vector<torch::Tensor> segments,
+    torch::Tensor offsets, torch::Tensor ids, torch::Tensor probes, int64_t k,
+    int64_t valid_n, int64_t tail_lo, int64_t tail_hi, int64_t max_list_len) {
+  // Exact top-k of each query over the rows of its probed lists plus the
+  // tail [tail_lo, tail_hi). max_list_len only sizes the grid (any value
+  // >= 0 gives the same result); rows short of k candidates come back padded
+  // with (NEG_INF, -1), which the Python op normalises.
+  return ivf_scan_topk_impl(queries, segments, offsets, ids, probes, k, valid_n,
+                            tail_lo, tail_hi, max_list_len, nullptr);
+}
+
+std::tuple<torch::Tensor, torch::Tensor> ivf_scan_topk_filtered(
+    torch::Tensor queries, std::vector<torch::Tensor> segments,
+    std::vector<torch::Tensor> labels, torch::Tensor want, torch::Tensor offsets,
+    torch::Tensor ids, torch::Tensor probes, int64_t k, int64_t valid_n,
+    int64_t tail_lo, int64_t tail_hi, int64_t max_list_len) {
+  // ivf_scan_topk over the candidates row r with want[b] < 0 || label(r) ==
+  // want[b]; labels: one i32 tensor per segment, want: i32 [B].
+  const IvfFilter f = ivf_filter(segments, labels, want, queries);
+  return ivf_scan_topk_impl(queries, segments, offsets, ids, probes, k, valid_n,
+                            tail_lo, tail_hi, max_list_len, &f);
 }
 
 std::tuple<torch::Tensor, torch::Tensor> ivf_search(
@@ -746,18 +835,26 @@ std::tuple<torch::Tensor, torch::Tensor> ivf_search(
   // those lists plus the tail [n_indexed, valid_n) (empty when valid_n is
   // a snapshot from before the index was built; listed ids >= valid_n are
   // dropped by the scan).
-  TORCH_CHECK(offsets.dim() == 1 && offsets.size(0) == centroids.size(0) + 1,
-              "offsets must have L+1 entries for L centroids");
-  TORCH_CHECK(ids.dim() == 1 && ids.size(0) == n_indexed,
-              "ids must have n_indexed entries");
-  TORCH_CHECK(n_indexed >= 0, "n_indexed must be >= 0");
-  const int64_t L = centroids.size(0);
-  TORCH_CHECK(nprobe >= 1 && nprobe <= L, "nprobe must be in [1, n_lists]");
-  auto scores = ivf_route_scores_op(queries, centroids);
-  auto probes = std::get<1>(scores.topk(nprobe, 1)).to(torch::kInt32).contiguous();
+  auto probes = ivf_route_probes(queries, centroids, offsets, ids, nprobe, n_indexed);
   return ivf_scan_topk(queries, std::move(segments), offsets, ids, probes, k,
                        valid_n, std::min(n_indexed, valid_n), valid_n,
                        max_list_len);
+}
+
+std::tuple<torch::Tensor, torch::Tensor> ivf_search_filtered(
+    torch::Tensor queries, std::vector<torch::Tensor> segments,
+    std::vector<torch::Tensor> labels, torch::Tensor want,
+    torch::Tensor centroids, torch::Tensor offsets, torch::Tensor ids,
+    int64_t nprobe, int64_t k, int64_t valid_n, int64_t n_indexed,
+    int64_t max_list_len) {
+  // ivf_search with the label predicate in the scan; the routing does not
+  // know labels. The filter is checked before the routing kernel runs.
+  ivf_filter(segments, labels, want, queries);
+  auto probes = ivf_route_probes(queries, centroids, offsets, ids, nprobe, n_indexed);
+  return ivf_scan_topk_filtered(queries, std::move(segments), std::move(labels),
+                                want, offsets, ids, probes, k, valid_n,
+                                std::min(n_indexed, valid_n), valid_n,
+                                max_list_len);
 }
 
 // ---- list-major (batched) routed scan --------------------------------------
@@ -804,13 +901,16 @@ std::vector<torch::Tensor> ivf_group_probes_op(torch::Tensor probes,
           n_tiles.to(torch::kInt32).contiguous()};
 }
 
-std::tuple<torch::Tensor, torch::Tensor> ivf_scan_topk_batched(
-    torch::Tensor queries, std::vector<torch::Tensor> segments,
-    torch::Tensor offsets, torch::Tensor ids, torch::Tensor probes, int64_t k,
-    int64_t valid_n, int64_t tail_lo, int64_t tail_hi, int64_t max_list_len) {
-  // ivf_scan_topk's contract through the list-major kernel: group the
-  // (query, probe) pairs by list, scan every (tile, slice) once with
-  // ivf_scan_grouped_kernel, finish with emit_merge_topk.
+namespace {
+
+// ivf_scan_topk_batched, and with a filter ivf_scan_topk_batched_filtered:
+// the same grouping, plan, candidate buffer and merge; only the scan kernel
+// differs.
+std::tuple<torch::Tensor, torch::Tensor> ivf_scan_topk_batched_impl(
+    const torch::Tensor& queries, const std::vector<torch::Tensor>& segments,
+    const torch::Tensor& offsets, const torch::Tensor& ids,
+    const torch::Tensor& probes, int64_t k, int64_t valid_n, int64_t tail_lo,
+    int64_t tail_hi, int64_t max_list_len, const IvfFilter* filter) {
   const IvfScanArgs a = ivf_scan_args(queries, segments, offsets, ids, probes, k,
                                       valid_n, tail_lo, tail_hi, max_list_len);
   const int B = a.B, D = a.D, L = a.L, nprobe = a.nprobe;
@@ -845,15 +945,27 @@ std::tuple<torch::Tensor, torch::Tensor> ivf_scan_topk_batched(
     // grid.y holds at most 65535 tiles
     for (long t0 = 0; t0 < p.max_tiles; t0 += 65535) {
       const int nt = (int)std::min(p.max_tiles - t0, 65535L);
-      hipLaunchKernelGGL(
-          ivf_scan_grouped_kernel, dim3(p.slices, nt), dim3(256), lds, stream,
-          (const bf16_t*)queries.data_ptr() + (size_t)b0 * D, a.segs,
-          (const long*)offsets.data_ptr<int64_t>(), ids.data_ptr<int>(),
-          grp[0].data_ptr<int>(), grp[1].data_ptr<int>(), tiles,
-          tiles + p.max_tiles, tiles + 2 * p.max_tiles, grp[3].data_ptr<int>(),
-          (int)t0, nb, nprobe + 1, L, (long)ids.size(0), D, (long)valid_n,
-          (long)tail_lo, (long)tail_hi, p.pairs,
-          (unsigned long long*)cand.data_ptr<int64_t>());
+      if (filter)
+        hipLaunchKernelGGL(
+            ivf_scan_grouped_filtered_kernel, dim3(p.slices, nt), dim3(256), lds,
+            stream, (const bf16_t*)queries.data_ptr() + (size_t)b0 * D, a.segs,
+            filter->labels, filter->want + b0,
+            (const long*)offsets.data_ptr<int64_t>(), ids.data_ptr<int>(),
+            grp[0].data_ptr<int>(), grp[1].data_ptr<int>(), tiles,
+            tiles + p.max_tiles, tiles + 2 * p.max_tiles, grp[3].data_ptr<int>(),
+            (int)t0, nb, nprobe + 1, L, (long)ids.size(0), D, (long)valid_n,
+            (long)tail_lo, (long)tail_hi, p.pairs,
+            (unsigned long long*)cand.data_ptr<int64_t>());
+      else
+        hipLaunchKernelGGL(
+            ivf_scan_grouped_kernel, dim3(p.slices, nt), dim3(256), lds, stream,
+            (const bf16_t*)queries.data_ptr() + (size_t)b0 * D, a.segs,
+            (const long*)offsets.data_ptr<int64_t>(), ids.data_ptr<int>(),
+            grp[0].data_ptr<int>(), grp[1].data_ptr<int>(), tiles,
+            tiles + p.max_tiles, tiles + 2 * p.max_tiles, grp[3].data_ptr<int>(),
+            (int)t0, nb, nprobe + 1, L, (long)ids.size(0), D, (long)valid_n,
+            (long)tail_lo, (long)tail_hi, p.pairs,
+            (unsigned long long*)cand.data_ptr<int64_t>());
     }
     hipLaunchKernelGGL(emit_merge_topk, dim3(nb), dim3(256), 0, stream,
                        (const unsigned long long*)cand.data_ptr<int64_t>(),
@@ -865,6 +977,45 @@ std::tuple<torch::Tensor, torch::Tensor> ivf_scan_topk_batched(
   return {out_score, out_idx};
 }
 
+}  // namespace
+
+std::tuple<torch::Tensor, torch::Tensor> ivf_scan_topk_batched(
+    torch::Tensor queries, std::vector<torch::Tensor> segments,
+    torch::Tensor offsets, torch::Tensor ids, torch::Tensor probes, int64_t k,
+    int64_t valid_n, int64_t tail_lo, int64_t tail_hi, int64_t max_list_len) {
+  // ivf_scan_topk's contract through the list-major kernel: group the
+  // (query, probe) pairs by list, scan every (tile, slice) once with
+  // ivf_scan_grouped_kernel, finish with emit_merge_topk.
+  return ivf_scan_topk_batched_impl(queries, segments, offsets, ids, probes, k,
+                                    valid_n, tail_lo, tail_hi, max_list_len,
+                                    nullptr);
+}
+
+std::tuple<torch::Tensor, torch::Tensor> ivf_scan_topk_batched_filtered(
+    torch::Tensor queries, std::vector<torch::Tensor> segments,
+    std::vector<torch::Tensor> labels, torch::Tensor want, torch::Tensor offsets,
+    torch::Tensor ids, torch::Tensor probes, int64_t k, int64_t valid_n,
+    int64_t tail_lo, int64_t tail_hi, int64_t max_list_len) {
+  // ivf_scan_topk_filtered's contract through the list-major kernel.
+  const IvfFilter f = ivf_filter(segments, labels, want, queries);
+  return ivf_scan_topk_batched_impl(queries, segments, offsets, ids, probes, k,
+                                    valid_n, tail_lo, tail_hi, max_list_len, &f);
+}
+
+std::tuple<torch::Tensor, torch::Tensor> ivf_search_batched_filtered(
+    torch::Tensor queries, std::vector<torch::Tensor> segments,
+    std::vector<torch::Tensor> labels, torch::Tensor want,
+    torch::Tensor centroids, torch::Tensor offsets, torch::Tensor ids,
+    int64_t nprobe, int64_t k, int64_t valid_n, int64_t n_indexed,
+    int64_t max_list_len) {
+  // ivf_search_filtered with the list-major scan.
+  ivf_filter(segments, labels, want, queries);
+  auto probes = ivf_route_probes(queries, centroids, offsets, ids, nprobe, n_indexed);
+  return ivf_scan_topk_batched_filtered(
+      queries, std::move(segments), std::move(labels), want, offsets, ids, probes,
+      k, valid_n, std::min(n_indexed, valid_n), valid_n, max_list_len);
+}
+
 std::tuple<torch::Tensor, torch::Tensor> ivf_search_batched(
     torch::Tensor queries, std::vector<torch::Tensor> segments,
     torch::Tensor centroids, torch::Tensor offsets, torch::Tensor ids,
@@ -872,15 +1023,7 @@ std::tuple<torch::Tensor, torch::Tensor> ivf_search_batched(
     int64_t max_list_len) {
   // ivf_search with the list-major scan: route -> select -> group -> scan
   // -> merge (the last three inside ivf_scan_topk_batched).
-  TORCH_CHECK(offsets.dim() == 1 && offsets.size(0) == centroids.size(0) + 1,
-              "offsets must have L+1 entries for L centroids");
-  TORCH_CHECK(ids.dim() == 1 && ids.size(0) == n_indexed,
-              "ids must have n_indexed entries");
-  TORCH_CHECK(n_indexed >= 0, "n_indexed must be >= 0");
-  const int64_t L = centroids.size(0);
-  TORCH_CHECK(nprobe >= 1 && nprobe <= L, "nprobe must be in [1, n_lists]");
-  auto scores = ivf_route_scores_op(queries, centroids);
-  auto probes = std::get<1>(scores.topk(nprobe, 1)).to(torch::kInt32).contiguous();
+  auto probes = ivf_route_probes(queries, centroids, offsets, ids, nprobe, n_indexed);
   return ivf_scan_topk_batched(queries, std::move(segments), offsets, ids, probes,
                                k, valid_n, std::min(n_indexed, valid_n), valid_n,
                                max_list_len);
@@ -929,6 +1072,38 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("ivf_search_batched", &ivf_search_batched,
         "cluster-routed (IVF) top-k search through the list-major MFMA scan",
         pybind11::arg("queries"), pybind11::arg("segments"),
+        pybind11::arg("centroids"), pybind11::arg("offsets"),
+        pybind11::arg("ids"), pybind11::arg("nprobe"), pybind11::arg("k"),
+        pybind11::arg("valid_n"), pybind11::arg("n_indexed"),
+        pybind11::arg("max_list_len") = (int64_t)0);
+  m.def("ivf_scan_topk_filtered", &ivf_scan_topk_filtered,
+        "ivf_scan_topk over the rows whose label matches each query's",
+        pybind11::arg("queries"), pybind11::arg("segments"),
+        pybind11::arg("labels"), pybind11::arg("want"),
+        pybind11::arg("offsets"), pybind11::arg("ids"), pybind11::arg("probes"),
+        pybind11::arg("k"), pybind11::arg("valid_n"), pybind11::arg("tail_lo"),
+        pybind11::arg("tail_hi"),
+        pybind11::arg("max_list_len") = (int64_t)0);
+  m.def("ivf_scan_topk_batched_filtered", &ivf_scan_topk_batched_filtered,
+        "ivf_scan_topk_filtered through the list-major MFMA scan",
+        pybind11::arg("queries"), pybind11::arg("segments"),
+        pybind11::arg("labels"), pybind11::arg("want"),
+        pybind11::arg("offsets"), pybind11::arg("ids"), pybind11::arg("probes"),
+        pybind11::arg("k"), pybind11::arg("valid_n"), pybind11::arg("tail_lo"),
+        pybind11::arg("tail_hi"),
+        pybind11::arg("max_list_len") = (int64_t)0);
+  m.def("ivf_search_filtered", &ivf_search_filtered,
+        "cluster-routed (IVF) top-k search over the rows of each query's label",
+        pybind11::arg("queries"), pybind11::arg("segments"),
+        pybind11::arg("labels"), pybind11::arg("want"),
+        pybind11::arg("centroids"), pybind11::arg("offsets"),
+        pybind11::arg("ids"), pybind11::arg("nprobe"), pybind11::arg("k"),
+        pybind11::arg("valid_n"), pybind11::arg("n_indexed"),
+        pybind11::arg("max_list_len") = (int64_t)0);
+  m.def("ivf_search_batched_filtered", &ivf_search_batched_filtered,
+        "ivf_search_filtered through the list-major MFMA scan",
+        pybind11::arg("queries"), pybind11::arg("segments"),
+        pybind11::arg("labels"), pybind11::arg("want"),
         pybind11::arg("centroids"), pybind11::arg("offsets"),
         pybind11::arg("ids"), pybind11::arg("nprobe"), pybind11::arg("k"),
         pybind11::arg("valid_n"), pybind11::arg("n_indexed"),

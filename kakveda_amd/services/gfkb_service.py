@@ -134,8 +134,9 @@ class UpsertPatternRequest(BaseModel):
 
 def _setup_routed(engine: GfkbEngine, config: Optional[Any]) -> None:
     """Apply the ``gfkb.routed`` config block: when enabled, build the routed
-    index at start-up if the store is big enough and make its ``nprobe`` the
-    engine default. Disabled (the default) touches nothing."""
+    index at start-up if the store is big enough, make its ``nprobe`` the
+    engine default and its ``filtered`` flag the engine's ``route_filtered``.
+    Disabled (the default) touches nothing."""
     if config is None:
         from kakveda_amd.core.config import ConfigStore
 
@@ -155,7 +156,15 @@ def _setup_routed(engine: GfkbEngine, config: Optional[Any]) -> None:
         return
     index = engine.build_index(n_lists=routed.get("n_lists"))
     engine.nprobe = int(routed.get("nprobe", 32))
-    logger.info("routed search on: nprobe=%d, index %s", engine.nprobe, index.stats)
+    # filter_first requests stay routed too (with the store's exact fill);
+    # off, a batch with one of them runs the exact filtered search
+    engine.route_filtered = bool(routed.get("filtered", False))
+    logger.info(
+        "routed search on: nprobe=%d, filtered=%s, index %s",
+        engine.nprobe,
+        engine.route_filtered,
+        index.stats,
+    )
 
 
 def create_app(
