@@ -25,9 +25,9 @@ Kernels (kakveda_amd/ops/hip/):
   ivf_scan_grouped_kernel gathers each probed list once per tile of 16
   queries and scores the tile with MFMA).
 - ivf_scan_topk_filtered / ivf_search_filtered — the routed search with the
-  label predicate of cosine_topk_filtered inside either scan (sibling
-  kernels; the unfiltered ones are untouched), so a filter-first request
-  can stay routed.
+  label predicate of cosine_topk_filtered inside either scan (the
+  ``FILTER`` instantiation of the same kernel template), so a filter-first
+  request can stay routed.
 
 Policy: on a CUDA(ROCm) device the HIP extension is REQUIRED — ops raise
 if it is missing rather than silently falling back to eager PyTorch. The
@@ -489,6 +489,93 @@ def _use_batched(batched: Optional[bool], B: int, D: int) -> bool:
     return bool(batched)
 
 
+def _label_list(labels, segments: list) -> list:
+    """``labels`` as one tensor per segment: a list is taken as it is, one
+    tensor is split at the segment boundaries."""
+    if not isinstance(labels, torch.Tensor):
+        return list(labels)
+    if len(segments) == 1:
+        return [labels]
+    return list(torch.split(labels, [int(s.shape[0]) for s in segments]))
+
+
+def _ivf_scan_ref(queries, segments, offsets, ids, probes, k, valid_n, tail_lo,
+                  tail_hi, labels=None, want=None):
+    """The routed scan in plain PyTorch (fp32 accumulate); ``labels=None,
+    want=None`` means unfiltered."""
+    segs = _segment_list(segments)
+    dev = queries.device
+    B = queries.shape[0]
+    L = int(offsets.shape[0]) - 1
+    off = offsets.to("cpu").long().tolist()
+    ids_l = ids.to(dev).long()
+    if labels is not None:
+        lab = torch.cat([l.to(dev).long().reshape(-1) for l in _label_list(labels, segs)])
+        w = want.to("cpu").long().tolist()
+    tail = torch.arange(int(tail_lo), int(tail_hi), dtype=torch.int64, device=dev)
+    out_s = torch.full((B, k), float("-inf"), dtype=torch.float32, device=dev)
+    out_i = torch.full((B, k), -1, dtype=torch.int64, device=dev)
+    for b, row in enumerate(probes.to("cpu").long().tolist()):
+        parts = [ids_l[off[l] : off[l + 1]] for l in row if 0 <= l < L]
+        rows = torch.cat(parts + [tail])
+        rows = rows[(rows >= 0) & (rows < int(valid_n))]
+        if labels is not None and w[b] >= 0:
+            rows = rows[lab[rows] == w[b]]
+        if rows.numel() == 0:
+            continue
+        sims = _gather_rows(segs, rows).float() @ queries[b].float()
+        kk = min(k, int(rows.numel()))
+        s, sel = torch.topk(sims, kk)
+        out_s[b, :kk] = s
+        out_i[b, :kk] = rows[sel]
+    return out_s, out_i
+
+
+def _ivf_search_ref(queries, segments, centroids, offsets, ids, nprobe, k, valid_n,
+                    n_indexed, labels=None, want=None):
+    """The routed search in plain PyTorch: route, then ``_ivf_scan_ref``."""
+    route = queries.float() @ centroids.float().t()
+    probes = torch.topk(route, min(int(nprobe), route.shape[1]), dim=1).indices
+    return _ivf_scan_ref(
+        queries, segments, offsets, ids, probes, k, valid_n,
+        min(int(n_indexed), int(valid_n)), valid_n, labels, want,
+    )
+
+
+def _ivf_gpu(op, batched, queries, segments, labels, want, pre, offsets, ids, mid, k, post):
+    """Run the extension's routed op ``op`` ("ivf_scan_topk" or "ivf_search",
+    its ``_batched`` form as ``batched`` says, its ``_filtered`` form when
+    ``labels`` is given) and normalise what it returns. The arguments follow
+    the extension's order: ``pre`` stands before ``offsets``, ``mid`` between
+    ``ids`` and ``k``, ``post`` (integers) after ``k``."""
+    ext = _require_ext()
+    dev = queries.device
+
+    def i32(t):
+        return t.to(device=dev, dtype=torch.int32).contiguous() if isinstance(t, torch.Tensor) else t
+
+    segs = _segment_list(segments)
+    if _use_batched(batched, queries.shape[0], queries.shape[1]):
+        op += "_batched"
+    filt = ()
+    if labels is not None:
+        op += "_filtered"
+        filt = ([i32(l) for l in _label_list(labels, segs)], i32(want))
+    scores, idx = getattr(ext, op)(
+        queries,
+        segs,
+        *filt,
+        *pre,
+        offsets.to(device=dev, dtype=torch.int64).contiguous(),
+        i32(ids),
+        i32(mid),
+        min(int(k), KMAX),
+        *(int(v) for v in post),
+    )
+    scores = torch.where(idx < 0, torch.full_like(scores, float("-inf")), scores)
+    return _pad_topk(scores, idx, k)
+
+
 def ivf_scan_topk_ref(
     queries: torch.Tensor,
     segments,
@@ -501,27 +588,7 @@ def ivf_scan_topk_ref(
     tail_hi: int,
 ) -> Tuple[torch.Tensor, torch.Tensor]:
     """Plain-PyTorch reference of ``ivf_scan_topk`` (fp32 accumulate)."""
-    segs = _segment_list(segments)
-    dev = queries.device
-    B = queries.shape[0]
-    L = int(offsets.shape[0]) - 1
-    off = offsets.to("cpu").long().tolist()
-    ids_l = ids.to(dev).long()
-    tail = torch.arange(int(tail_lo), int(tail_hi), dtype=torch.int64, device=dev)
-    out_s = torch.full((B, k), float("-inf"), dtype=torch.float32, device=dev)
-    out_i = torch.full((B, k), -1, dtype=torch.int64, device=dev)
-    for b, row in enumerate(probes.to("cpu").long().tolist()):
-        parts = [ids_l[off[l] : off[l + 1]] for l in row if 0 <= l < L]
-        rows = torch.cat(parts + [tail])
-        rows = rows[(rows >= 0) & (rows < int(valid_n))]
-        if rows.numel() == 0:
-            continue
-        sims = _gather_rows(segs, rows).float() @ queries[b].float()
-        kk = min(k, int(rows.numel()))
-        s, sel = torch.topk(sims, kk)
-        out_s[b, :kk] = s
-        out_i[b, :kk] = rows[sel]
-    return out_s, out_i
+    return _ivf_scan_ref(queries, segments, offsets, ids, probes, k, valid_n, tail_lo, tail_hi)
 
 
 def ivf_scan_topk(
@@ -558,27 +625,11 @@ def ivf_scan_topk(
     every value runs the reference.
     """
     if queries.device.type != "cuda":
-        return ivf_scan_topk_ref(
-            queries, segments, offsets, ids, probes, k, valid_n, tail_lo, tail_hi
-        )
-    ext = _require_ext()
-    dev = queries.device
-    kk = min(int(k), KMAX)
-    scan = ext.ivf_scan_topk_batched if _use_batched(batched, queries.shape[0], queries.shape[1]) else ext.ivf_scan_topk
-    scores, idx = scan(
-        queries,
-        _segment_list(segments),
-        offsets.to(device=dev, dtype=torch.int64).contiguous(),
-        ids.to(device=dev, dtype=torch.int32).contiguous(),
-        probes.to(device=dev, dtype=torch.int32).contiguous(),
-        kk,
-        int(valid_n),
-        int(tail_lo),
-        int(tail_hi),
-        int(max_list_len),
+        return _ivf_scan_ref(queries, segments, offsets, ids, probes, k, valid_n, tail_lo, tail_hi)
+    return _ivf_gpu(
+        "ivf_scan_topk", batched, queries, segments, None, None, (), offsets, ids,
+        probes, k, (valid_n, tail_lo, tail_hi, max_list_len),
     )
-    scores = torch.where(idx < 0, torch.full_like(scores, float("-inf")), scores)
-    return _pad_topk(scores, idx, k)
 
 
 def ivf_search_ref(
@@ -593,11 +644,8 @@ def ivf_search_ref(
     n_indexed: int,
 ) -> Tuple[torch.Tensor, torch.Tensor]:
     """Plain-PyTorch reference of ``ivf_search`` (fp32 accumulate)."""
-    route = queries.float() @ centroids.float().t()
-    probes = torch.topk(route, min(int(nprobe), route.shape[1]), dim=1).indices
-    return ivf_scan_topk_ref(
-        queries, segments, offsets, ids, probes, k, valid_n,
-        min(int(n_indexed), int(valid_n)), valid_n,
+    return _ivf_search_ref(
+        queries, segments, centroids, offsets, ids, nprobe, k, valid_n, n_indexed
     )
 
 
@@ -623,27 +671,13 @@ def ivf_search(
     L = int(centroids.shape[0])
     nprobe = max(1, min(int(nprobe), L))
     if queries.device.type != "cuda":
-        return ivf_search_ref(
+        return _ivf_search_ref(
             queries, segments, centroids, offsets, ids, nprobe, k, valid_n, n_indexed
         )
-    ext = _require_ext()
-    dev = queries.device
-    kk = min(int(k), KMAX)
-    search = ext.ivf_search_batched if _use_batched(batched, queries.shape[0], queries.shape[1]) else ext.ivf_search
-    scores, idx = search(
-        queries,
-        _segment_list(segments),
-        centroids,
-        offsets.to(device=dev, dtype=torch.int64).contiguous(),
-        ids.to(device=dev, dtype=torch.int32).contiguous(),
-        nprobe,
-        kk,
-        int(valid_n),
-        int(n_indexed),
-        int(max_list_len),
+    return _ivf_gpu(
+        "ivf_search", batched, queries, segments, None, None, (centroids,), offsets,
+        ids, nprobe, k, (valid_n, n_indexed, max_list_len),
     )
-    scores = torch.where(idx < 0, torch.full_like(scores, float("-inf")), scores)
-    return _pad_topk(scores, idx, k)
 
 
 # ---------------------------------------------------------------------------
@@ -662,16 +696,6 @@ IVF_FILTERED_SPARSE_SHARE = 0.01
 IVF_FILTERED_SPARSE_MIN_B = 1024
 
 
-def _label_list(labels, segments: list) -> list:
-    """``labels`` as one tensor per segment: a list is taken as it is, one
-    tensor is split at the segment boundaries."""
-    if not isinstance(labels, torch.Tensor):
-        return list(labels)
-    if len(segments) == 1:
-        return [labels]
-    return list(torch.split(labels, [int(s.shape[0]) for s in segments]))
-
-
 def ivf_scan_topk_filtered_ref(
     queries: torch.Tensor,
     segments,
@@ -688,31 +712,9 @@ def ivf_scan_topk_filtered_ref(
     """Plain-PyTorch reference of ``ivf_scan_topk_filtered`` (fp32
     accumulate): ``ivf_scan_topk_ref`` over the candidates whose label the
     query wants."""
-    segs = _segment_list(segments)
-    dev = queries.device
-    B = queries.shape[0]
-    L = int(offsets.shape[0]) - 1
-    off = offsets.to("cpu").long().tolist()
-    ids_l = ids.to(dev).long()
-    lab = torch.cat([l.to(dev).long().reshape(-1) for l in _label_list(labels, segs)])
-    w = want.to("cpu").long().tolist()
-    tail = torch.arange(int(tail_lo), int(tail_hi), dtype=torch.int64, device=dev)
-    out_s = torch.full((B, k), float("-inf"), dtype=torch.float32, device=dev)
-    out_i = torch.full((B, k), -1, dtype=torch.int64, device=dev)
-    for b, row in enumerate(probes.to("cpu").long().tolist()):
-        parts = [ids_l[off[l] : off[l + 1]] for l in row if 0 <= l < L]
-        rows = torch.cat(parts + [tail])
-        rows = rows[(rows >= 0) & (rows < int(valid_n))]
-        if w[b] >= 0:
-            rows = rows[lab[rows] == w[b]]
-        if rows.numel() == 0:
-            continue
-        sims = _gather_rows(segs, rows).float() @ queries[b].float()
-        kk = min(k, int(rows.numel()))
-        s, sel = torch.topk(sims, kk)
-        out_s[b, :kk] = s
-        out_i[b, :kk] = rows[sel]
-    return out_s, out_i
+    return _ivf_scan_ref(
+        queries, segments, offsets, ids, probes, k, valid_n, tail_lo, tail_hi, labels, want
+    )
 
 
 def ivf_scan_topk_filtered(
@@ -745,35 +747,13 @@ def ivf_scan_topk_filtered(
     result is that op's.
     """
     if queries.device.type != "cuda":
-        return ivf_scan_topk_filtered_ref(
-            queries, segments, labels, want, offsets, ids, probes, k, valid_n,
-            tail_lo, tail_hi,
+        return _ivf_scan_ref(
+            queries, segments, offsets, ids, probes, k, valid_n, tail_lo, tail_hi, labels, want
         )
-    ext = _require_ext()
-    dev = queries.device
-    kk = min(int(k), KMAX)
-    segs = _segment_list(segments)
-    scan = (
-        ext.ivf_scan_topk_batched_filtered
-        if _use_batched(batched, queries.shape[0], queries.shape[1])
-        else ext.ivf_scan_topk_filtered
+    return _ivf_gpu(
+        "ivf_scan_topk", batched, queries, segments, labels, want, (), offsets, ids,
+        probes, k, (valid_n, tail_lo, tail_hi, max_list_len),
     )
-    scores, idx = scan(
-        queries,
-        segs,
-        [l.to(device=dev, dtype=torch.int32).contiguous() for l in _label_list(labels, segs)],
-        want.to(device=dev, dtype=torch.int32).contiguous(),
-        offsets.to(device=dev, dtype=torch.int64).contiguous(),
-        ids.to(device=dev, dtype=torch.int32).contiguous(),
-        probes.to(device=dev, dtype=torch.int32).contiguous(),
-        kk,
-        int(valid_n),
-        int(tail_lo),
-        int(tail_hi),
-        int(max_list_len),
-    )
-    scores = torch.where(idx < 0, torch.full_like(scores, float("-inf")), scores)
-    return _pad_topk(scores, idx, k)
 
 
 def ivf_search_filtered_ref(
@@ -790,11 +770,8 @@ def ivf_search_filtered_ref(
     n_indexed: int,
 ) -> Tuple[torch.Tensor, torch.Tensor]:
     """Plain-PyTorch reference of ``ivf_search_filtered`` (fp32 accumulate)."""
-    route = queries.float() @ centroids.float().t()
-    probes = torch.topk(route, min(int(nprobe), route.shape[1]), dim=1).indices
-    return ivf_scan_topk_filtered_ref(
-        queries, segments, labels, want, offsets, ids, probes, k, valid_n,
-        min(int(n_indexed), int(valid_n)), valid_n,
+    return _ivf_search_ref(
+        queries, segments, centroids, offsets, ids, nprobe, k, valid_n, n_indexed, labels, want
     )
 
 
@@ -824,32 +801,10 @@ def ivf_search_filtered(
     L = int(centroids.shape[0])
     nprobe = max(1, min(int(nprobe), L))
     if queries.device.type != "cuda":
-        return ivf_search_filtered_ref(
-            queries, segments, labels, want, centroids, offsets, ids, nprobe, k,
-            valid_n, n_indexed,
+        return _ivf_search_ref(
+            queries, segments, centroids, offsets, ids, nprobe, k, valid_n, n_indexed, labels, want
         )
-    ext = _require_ext()
-    dev = queries.device
-    kk = min(int(k), KMAX)
-    segs = _segment_list(segments)
-    search = (
-        ext.ivf_search_batched_filtered
-        if _use_batched(batched, queries.shape[0], queries.shape[1])
-        else ext.ivf_search_filtered
+    return _ivf_gpu(
+        "ivf_search", batched, queries, segments, labels, want, (centroids,), offsets,
+        ids, nprobe, k, (valid_n, n_indexed, max_list_len),
     )
-    scores, idx = search(
-        queries,
-        segs,
-        [l.to(device=dev, dtype=torch.int32).contiguous() for l in _label_list(labels, segs)],
-        want.to(device=dev, dtype=torch.int32).contiguous(),
-        centroids,
-        offsets.to(device=dev, dtype=torch.int64).contiguous(),
-        ids.to(device=dev, dtype=torch.int32).contiguous(),
-        nprobe,
-        kk,
-        int(valid_n),
-        int(n_indexed),
-        int(max_list_len),
-    )
-    scores = torch.where(idx < 0, torch.full_like(scores, float("-inf")), scores)
-    return _pad_topk(scores, idx, k)

@@ -1,7 +1,7 @@
 // List-major (batched) routed scan. Included by kakveda_kernels.hip after
-// ivf_impl.h (IvfSegs, bf16x8 / f32x4 / enc_f32 come from there and from
-// kernels_impl.h). Nothing here shares a body with the kernels of those
-// headers, so their machine code does not move.
+// ivf_impl.h (IvfSegs, IvfFilterArg, bf16x8 / f32x4 / enc_f32 come from there
+// and from kernels_impl.h). Nothing here shares a body with the kernels of
+// those headers, so their machine code does not move.
 //
 // ivf_scan_topk_kernel runs one block per (query, probed list, slice): a list
 // that 40 queries of a batch probe is gathered 40 times and scored with
@@ -21,9 +21,11 @@ namespace kakveda {
 // apart and cover the 64 banks once
 DEVINL int ivf_batch_qpitch(int D) { return D / 8 + 1; }
 
+constexpr int IVF_BATCH_GROUP_LINES = 4;  // 128-byte lines per load group
+
 // ---------------------------------------------------------------------------
-// ivf_scan_grouped_kernel: grid = (slices, tiles), 256 threads, dynamic
-// LDS = QTILE * (D*2 + 16) bytes (the tile's queries).
+// ivf_scan_grouped_kernel<FILTER>: grid = (slices, tiles), 256 threads,
+// dynamic LDS = QTILE * (D*2 + 16) bytes (the tile's queries).
 //
 // Tile t = (list tile_list[t], pairs [tile_first[t], + tile_count[t])); list
 // == L is the tail [tail_lo, tail_hi). Blocks with t >= *n_tiles, an empty
@@ -62,211 +64,28 @@ DEVINL int ivf_batch_qpitch(int D) { return D / 8 + 1; }
 // inserted; pad lanes of a short tile hold the tile's first query and store
 // nothing. valid_n >= 1 and every row below it lies in a checked segment.
 //
-// Resource usage: the comment above the kernel's definition.
+// FILTER adds the label predicate of cosine_topk_filtered (row r is eligible
+// for query b iff want[b] < 0 || label(r) == want[b]). The tile's wants sit
+// in LDS beside pq[]. locate() fetches the row's label with its id (it runs
+// one step ahead of the multiply, so neither load is on the critical path;
+// a row not to be inserted reads row 0's label), and the shuffle that hands
+// rid to the four result rows of a lane carries the label too; eligibility
+// is tested per (query, row) at insertion. A tile mixes wants, so row loads
+// stay unconditional: a row that no query of the tile wants is still
+// gathered and multiplied.
+//
+// gfx950, hipcc -O3, no spills and no scratch in either instantiation.
+// Unfiltered: 116 VGPRs + 4 AGPRs (120 of 512: 4 waves per SIMD); 16,448 B
+// static LDS (the merge lists and pq) plus QTILE * (2D + 16) dynamic: 41,280 B
+// at D = 768, so LDS sets the occupancy there at 3 blocks = 12 waves per CU
+// (3 per SIMD), each with 8 KiB of row loads in flight. Filtered: 120 VGPRs
+// + 4 AGPRs (124 of 512, still 4 waves per SIMD); 16,512 B static LDS (pw
+// too), 41,344 B at D = 768: the same 3 blocks per CU.
 // ---------------------------------------------------------------------------
-constexpr int IVF_BATCH_GROUP_LINES = 4;  // 128-byte lines per load group
-
-// gfx950, hipcc -O3: 116 VGPRs + 4 AGPRs (120 of 512: 4 waves per SIMD), no
-// spills, no scratch; 16,448 B static LDS (the merge lists and pq) plus
-// QTILE * (2D + 16) dynamic: 41,280 B at D = 768, so LDS sets the occupancy
-// there at 3 blocks = 12 waves per CU (3 per SIMD), each with 8 KiB of row
-// loads in flight.
+template <bool FILTER>
 __global__ __launch_bounds__(256) void ivf_scan_grouped_kernel(
     const bf16_t* __restrict__ Q, const IvfSegs segs,
-    const long* __restrict__ offsets, const int* __restrict__ ids,
-    const int* __restrict__ pair_query, const int* __restrict__ pair_slot,
-    const int* __restrict__ tile_list, const int* __restrict__ tile_first,
-    const int* __restrict__ tile_count, const int* __restrict__ n_tiles,
-    int tile0, int B, int sources, int L, long n_ids, int D, long valid_n, long tail_lo,
-    long tail_hi, long n_pairs, unsigned long long* __restrict__ cand) {
-  extern __shared__ char ivf_bq[];  // [QTILE][D/8 + 1] bf16x8: the queries
-  __shared__ unsigned long long all[IVF_BATCH_QTILE * 16 * KMAX];
-  __shared__ int pq[IVF_BATCH_QTILE];  // query of each pair of the tile
-  const int t = tile0 + blockIdx.y;  // grid.y holds 65535 tiles a launch
-  const int tid = threadIdx.x;
-  if (t >= *n_tiles) return;
-  const int cnt = tile_count[t];
-  const int l = tile_list[t];
-  const long first = tile_first[t];
-  if (cnt < 1 || cnt > IVF_BATCH_QTILE || l < 0 || l > L || first < 0 ||
-      first + cnt > n_pairs)
-    return;
-
-  long lo, len;
-  const bool is_tail = l == L;
-  if (is_tail) {
-    lo = tail_lo;
-    len = tail_hi - tail_lo;
-  } else {
-    lo = offsets[l];
-    long hi = offsets[l + 1];
-    lo = lo < 0 ? 0 : lo;
-    hi = hi > n_ids ? n_ids : hi;
-    len = hi - lo;
-  }
-  // nothing in this slice (block-uniform): the slots stay preset-empty
-  if ((long)blockIdx.x * IVF_BATCH_BLOCK_ROWS >= len) return;
-
-  if (tid < IVF_BATCH_QTILE) {
-    const int b = pair_query[first + (tid < cnt ? tid : 0)];
-    pq[tid] = b >= 0 && b < B ? b : -1;
-  }
-  __syncthreads();
-  const int pitch = ivf_batch_qpitch(D);
-  const int d8 = D / 8;
-  for (int i = tid; i < IVF_BATCH_QTILE * d8; i += 256) {
-    const int c = i / d8, j = i - c * d8;
-    const int b = pq[c] < 0 ? 0 : pq[c];
-    ((bf16x8*)ivf_bq)[c * pitch + j] = ((const bf16x8*)(Q + (size_t)b * D))[j];
-  }
-  __syncthreads();
-
-  const int lane = tid & 63;
-  const int wid = tid >> 6;
-  const int rr = lane & 15;  // A: row of this wave's 16; B and D: query
-  const int g = lane >> 4;   // k group of the operands; D: rows 4g .. 4g+3
-  const bf16x8* qrow = (const bf16x8*)ivf_bq + rr * pitch + g;
-  const int nlines = D / 64;
-  const int ngroups = nlines / IVF_BATCH_GROUP_LINES;
-  constexpr int GL = 2 * IVF_BATCH_GROUP_LINES;  // loads (MFMA steps) per group
-
-  // the row position p of this lane: its id (-1: not to be inserted) and
-  // the address of its row (row 0 when not to be inserted), bf16x8 units
-  auto locate = [&](long p, int& rid) -> const bf16x8* {
-    const long pc = p < len ? p : len - 1;  // clamp loads past the end
-    const long r = is_tail ? lo + pc : (long)ids[lo + pc];
-    const bool ok = p < len && r >= 0 && r < valid_n;
-    const long rc = ok ? r : 0;
-    rid = ok ? (int)r : -1;
-    const int si = ivf_segment_of(rc, segs.s0, segs.q);
-    return (const bf16x8*)(segs.base[si] +
-                           ivf_local_row(rc, segs.s0, segs.q) * D) + g;
-  };
-
-  unsigned long long loc[KMAX];  // sorted desc; 0 = empty
-#pragma unroll
-  for (int q = 0; q < KMAX; ++q) loc[q] = 0ull;
-  const bool live = rr < cnt && pq[rr] >= 0;  // this lane's query is a pair
-
-  const long step = (long)gridDim.x * IVF_BATCH_BLOCK_ROWS;
-  long p0 = (long)blockIdx.x * IVF_BATCH_BLOCK_ROWS + wid * 16;
-  int rid = -1, rid_next = -1;
-  const bf16x8* row = locate(p0 + rr, rid);
-  bf16x8 cur[GL], nxt[GL];
-  if (ngroups > 0) {
-#pragma unroll
-    for (int v = 0; v < GL; ++v) cur[v] = row[v * 4];
-  }
-  for (; p0 < len; p0 += step) {
-    // the next 16 rows of this wave (a clamped, valid address past the end)
-    const bf16x8* row_next = locate(p0 + step + rr, rid_next);
-    f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
-    for (int gi = 0; gi < ngroups; ++gi) {
-      const bf16x8* src = gi + 1 < ngroups ? row + (gi + 1) * GL * 4 : row_next;
-#pragma unroll
-      for (int v = 0; v < GL; ++v) nxt[v] = src[v * 4];
-#pragma unroll
-      for (int v = 0; v < GL; ++v)
-        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-            cur[v], qrow[(gi * GL + v) * 4], acc, 0, 0, 0);
-#pragma unroll
-      for (int v = 0; v < GL; ++v) cur[v] = nxt[v];
-    }
-    for (int ln = ngroups * IVF_BATCH_GROUP_LINES; ln < nlines; ++ln) {
-      const bf16x8 a0 = row[ln * 8], a1 = row[ln * 8 + 4];
-      acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0, qrow[ln * 8], acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1, qrow[ln * 8 + 4], acc, 0,
-                                                    0, 0);
-    }
-    // acc[e]: query rr against row 4g + e of the wave's 16, whose id lane
-    // 4g + e holds
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const int r = __shfl(rid, 4 * g + e, 64);
-      const unsigned long long v =
-          live && r >= 0 ? ((unsigned long long)enc_f32(acc[e]) << 32) |
-                               (unsigned)(0x7fffffff - r)
-                         : 0ull;
-      if (v > loc[KMAX - 1]) {
-        loc[KMAX - 1] = v;  // insert at tail, bubble up (array stays sorted)
-#pragma unroll
-        for (int q = KMAX - 1; q > 0; --q)
-          if (loc[q] > loc[q - 1]) {
-            const unsigned long long tmp = loc[q];
-            loc[q] = loc[q - 1];
-            loc[q - 1] = tmp;
-          }
-      }
-    }
-    row = row_next;
-    rid = rid_next;
-  }
-
-  // per query rr: 16 sorted lists (wave wid, group g) -> the block's top-KMAX
-  {
-    const int j = wid * 4 + g;
-#pragma unroll
-    for (int q = 0; q < KMAX; ++q) all[(rr * 16 + j) * KMAX + q] = loc[q];
-  }
-  __syncthreads();
-  for (int stride = 8; stride >= 1; stride >>= 1) {
-    if (tid < IVF_BATCH_QTILE * stride) {
-      const int c = tid / stride, j = tid - c * stride;
-      // two-pointer merge of two sorted-desc KMAX lists -> top KMAX
-      // (LDS-indexed, as in emit_merge_topk)
-      unsigned long long* pa = all + (size_t)(c * 16 + j) * KMAX;
-      const unsigned long long* pb = all + (size_t)(c * 16 + j + stride) * KMAX;
-      unsigned long long o[KMAX];
-      int ia = 0, ib = 0;
-#pragma unroll
-      for (int q = 0; q < KMAX; ++q) {
-        const unsigned long long va = pa[ia], vb = pb[ib];
-        if (va >= vb) {
-          o[q] = va;
-          ++ia;
-        } else {
-          o[q] = vb;
-          ++ib;
-        }
-      }
-#pragma unroll
-      for (int q = 0; q < KMAX; ++q) pa[q] = o[q];
-    }
-    __syncthreads();
-  }
-  if (tid < IVF_BATCH_QTILE * KMAX) {
-    const int c = tid / KMAX, e = tid - c * KMAX;
-    if (c < cnt && pq[c] >= 0) {
-      const int y = pair_slot[first + c];
-      if (y >= 0 && y < sources)
-        cand[(((size_t)pq[c] * sources + y) * gridDim.x + blockIdx.x) * KMAX + e] =
-            all[(size_t)c * 16 * KMAX + e];
-    }
-  }
-}
-
-// ---------------------------------------------------------------------------
-// ivf_scan_grouped_filtered_kernel: ivf_scan_grouped_kernel with the label
-// predicate of cosine_topk_filtered (row r is eligible for query b iff
-// want[b] < 0 || label(r) == want[b]). A sibling kernel: the unfiltered one's
-// text does not change. Grid, dynamic LDS, candidate slots and merge are the
-// same.
-//
-// The tile's wants sit in LDS beside pq[]. locate() fetches the row's label
-// with its id (it runs one step ahead of the multiply, so neither load is on
-// the critical path), and the shuffle that hands rid to the four result rows
-// of a lane carries the label too; eligibility is tested per (query, row) at
-// insertion. A tile mixes wants, so row loads stay unconditional: a row that
-// no query of the tile wants is still gathered and multiplied.
-//
-// gfx950, hipcc -O3: 120 VGPRs + 4 AGPRs (124 of 512: 4 waves per SIMD), no
-// spills, no scratch; 16,512 B static LDS (the merge lists, pq and pw) plus
-// QTILE * (2D + 16) dynamic: 41,344 B at D = 768, so LDS sets the occupancy
-// there at 3 blocks = 12 waves per CU, as for the unfiltered kernel.
-// ---------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void ivf_scan_grouped_filtered_kernel(
-    const bf16_t* __restrict__ Q, const IvfSegs segs, const IvfLabels labels,
-    const int* __restrict__ want, const long* __restrict__ offsets,
+    const IvfFilterArg<FILTER> filt, const long* __restrict__ offsets,
     const int* __restrict__ ids, const int* __restrict__ pair_query,
     const int* __restrict__ pair_slot, const int* __restrict__ tile_list,
     const int* __restrict__ tile_first, const int* __restrict__ tile_count,
@@ -276,7 +95,8 @@ __global__ __launch_bounds__(256) void ivf_scan_grouped_filtered_kernel(
   extern __shared__ char ivf_bq[];  // [QTILE][D/8 + 1] bf16x8: the queries
   __shared__ unsigned long long all[IVF_BATCH_QTILE * 16 * KMAX];
   __shared__ int pq[IVF_BATCH_QTILE];  // query of each pair of the tile
-  __shared__ int pw[IVF_BATCH_QTILE];  // and the label it wants (< 0: any)
+  // FILTER: and the label it wants (< 0: any)
+  __shared__ int pw[FILTER ? IVF_BATCH_QTILE : 1];
   const int t = tile0 + blockIdx.y;  // grid.y holds 65535 tiles a launch
   const int tid = threadIdx.x;
   if (t >= *n_tiles) return;
@@ -306,7 +126,7 @@ __global__ __launch_bounds__(256) void ivf_scan_grouped_filtered_kernel(
     const int b = pair_query[first + (tid < cnt ? tid : 0)];
     const bool in = b >= 0 && b < B;
     pq[tid] = in ? b : -1;
-    pw[tid] = in ? want[b] : -1;
+    if constexpr (FILTER) pw[tid] = in ? filt.want[b] : -1;
   }
   __syncthreads();
   const int pitch = ivf_batch_qpitch(D);
@@ -327,9 +147,9 @@ __global__ __launch_bounds__(256) void ivf_scan_grouped_filtered_kernel(
   const int ngroups = nlines / IVF_BATCH_GROUP_LINES;
   constexpr int GL = 2 * IVF_BATCH_GROUP_LINES;  // loads (MFMA steps) per group
 
-  // the row position p of this lane: its id (-1: not to be inserted), its
-  // label (row 0's when not to be inserted) and the address of its row (row
-  // 0 when not to be inserted), bf16x8 units
+  // the row position p of this lane: its id (-1: not to be inserted), with
+  // FILTER its label (row 0's when not to be inserted), and the address of
+  // its row (row 0 when not to be inserted), bf16x8 units
   auto locate = [&](long p, int& rid, int& lab) -> const bf16x8* {
     const long pc = p < len ? p : len - 1;  // clamp loads past the end
     const long r = is_tail ? lo + pc : (long)ids[lo + pc];
@@ -338,7 +158,7 @@ __global__ __launch_bounds__(256) void ivf_scan_grouped_filtered_kernel(
     rid = ok ? (int)r : -1;
     const int si = ivf_segment_of(rc, segs.s0, segs.q);
     const long lr = ivf_local_row(rc, segs.s0, segs.q);
-    lab = labels.base[si][lr];
+    if constexpr (FILTER) lab = filt.labels.base[si][lr];
     return (const bf16x8*)(segs.base[si] + lr * D) + g;
   };
 
@@ -346,7 +166,8 @@ __global__ __launch_bounds__(256) void ivf_scan_grouped_filtered_kernel(
 #pragma unroll
   for (int q = 0; q < KMAX; ++q) loc[q] = 0ull;
   const bool live = rr < cnt && pq[rr] >= 0;  // this lane's query is a pair
-  const int w = pw[rr];                       // the label that query wants
+  int w = -1;                                 // the label that query wants
+  if constexpr (FILTER) w = pw[rr];
 
   const long step = (long)gridDim.x * IVF_BATCH_BLOCK_ROWS;
   long p0 = (long)blockIdx.x * IVF_BATCH_BLOCK_ROWS + wid * 16;
@@ -378,12 +199,12 @@ __global__ __launch_bounds__(256) void ivf_scan_grouped_filtered_kernel(
       acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1, qrow[ln * 8 + 4], acc, 0,
                                                     0, 0);
     }
-    // acc[e]: query rr against row 4g + e of the wave's 16, whose id and
-    // label lane 4g + e holds
+    // acc[e]: query rr against row 4g + e of the wave's 16, whose id (and
+    // label) lane 4g + e holds
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       const int r = __shfl(rid, 4 * g + e, 64);
-      const int rl = __shfl(lab, 4 * g + e, 64);
+      const int rl = FILTER ? __shfl(lab, 4 * g + e, 64) : -1;
       const unsigned long long v =
           live && r >= 0 && (w < 0 || rl == w)
               ? ((unsigned long long)enc_f32(acc[e]) << 32) |

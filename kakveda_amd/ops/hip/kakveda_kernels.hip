@@ -691,19 +691,15 @@ IvfScanArgs ivf_scan_args(const torch::Tensor& queries,
 // per-segment label pointers and the per-query wants. Refuses, before
 // anything is launched, labels the kernels' row -> segment function would
 // address out of bounds.
-struct IvfFilter {
-  IvfLabels labels;
-  const int* want;
-};
-
-IvfFilter ivf_filter(const std::vector<torch::Tensor>& segments,
-                     const std::vector<torch::Tensor>& labels,
-                     const torch::Tensor& want, const torch::Tensor& queries) {
+IvfFilterArg<true> ivf_filter(const std::vector<torch::Tensor>& segments,
+                              const std::vector<torch::Tensor>& labels,
+                              const torch::Tensor& want,
+                              const torch::Tensor& queries) {
   TORCH_CHECK(labels.size() == segments.size(), "labels needs one tensor per segment (",
               segments.size(), "), got ", labels.size());
   TORCH_CHECK(!segments.empty() && segments.size() <= (size_t)IVF_MAX_SEGMENTS,
               "routed search supports 1 to ", IVF_MAX_SEGMENTS, " store segments");
-  IvfFilter f{};
+  IvfFilterArg<true> f{};
   const int n = (int)labels.size();
   for (int i = 0; i < n; ++i) {
     check_i32_gpu(labels[i], 1, "labels");
@@ -725,13 +721,21 @@ IvfFilter ivf_filter(const std::vector<torch::Tensor>& segments,
   return f;
 }
 
+// The filter of the launch whose first query is b0.
+IvfFilterArg<false> ivf_filter_from(IvfFilterArg<false> f, int) { return f; }
+IvfFilterArg<true> ivf_filter_from(IvfFilterArg<true> f, int b0) {
+  f.want += b0;
+  return f;
+}
+
 // ivf_scan_topk, and with a filter ivf_scan_topk_filtered: the same plan,
-// candidate buffer and merge; only the scan kernel differs.
+// candidate buffer and merge; FILTER picks the kernel's instantiation.
+template <bool FILTER>
 std::tuple<torch::Tensor, torch::Tensor> ivf_scan_topk_impl(
     const torch::Tensor& queries, const std::vector<torch::Tensor>& segments,
     const torch::Tensor& offsets, const torch::Tensor& ids,
     const torch::Tensor& probes, int64_t k, int64_t valid_n, int64_t tail_lo,
-    int64_t tail_hi, int64_t max_list_len, const IvfFilter* filter) {
+    int64_t tail_hi, int64_t max_list_len, const IvfFilterArg<FILTER>& filter) {
   const IvfScanArgs a = ivf_scan_args(queries, segments, offsets, ids, probes, k,
                                       valid_n, tail_lo, tail_hi, max_list_len);
   const IvfSegs& segs = a.segs;
@@ -754,23 +758,14 @@ std::tuple<torch::Tensor, torch::Tensor> ivf_scan_topk_impl(
     auto ccount = torch::full(
         {(long)nb}, (int64_t)p.cand_entries,
         torch::TensorOptions().dtype(torch::kInt32).device(dev));
-    if (filter)
-      hipLaunchKernelGGL(
-          ivf_scan_topk_filtered_kernel, dim3(p.slices, p.sources, nb), dim3(256),
-          (size_t)D * 2, stream, (const bf16_t*)queries.data_ptr() + (size_t)b0 * D,
-          segs, filter->labels, filter->want + b0,
-          (const long*)offsets.data_ptr<int64_t>(), ids.data_ptr<int>(),
-          probes.data_ptr<int>() + (size_t)b0 * nprobe, nprobe, L,
-          (long)ids.size(0), D, (long)valid_n, (long)tail_lo, (long)tail_hi,
-          (unsigned long long*)cand.data_ptr<int64_t>());
-    else
-      hipLaunchKernelGGL(
-          ivf_scan_topk_kernel, dim3(p.slices, p.sources, nb), dim3(256),
-          (size_t)D * 2, stream, (const bf16_t*)queries.data_ptr() + (size_t)b0 * D,
-          segs, (const long*)offsets.data_ptr<int64_t>(), ids.data_ptr<int>(),
-          probes.data_ptr<int>() + (size_t)b0 * nprobe, nprobe, L,
-          (long)ids.size(0), D, (long)valid_n, (long)tail_lo, (long)tail_hi,
-          (unsigned long long*)cand.data_ptr<int64_t>());
+    hipLaunchKernelGGL(
+        ivf_scan_topk_kernel<FILTER>, dim3(p.slices, p.sources, nb), dim3(256),
+        (size_t)D * 2, stream, (const bf16_t*)queries.data_ptr() + (size_t)b0 * D,
+        segs, ivf_filter_from(filter, b0),
+        (const long*)offsets.data_ptr<int64_t>(), ids.data_ptr<int>(),
+        probes.data_ptr<int>() + (size_t)b0 * nprobe, nprobe, L,
+        (long)ids.size(0), D, (long)valid_n, (long)tail_lo, (long)tail_hi,
+        (unsigned long long*)cand.data_ptr<int64_t>());
     hipLaunchKernelGGL(emit_merge_topk, dim3(nb), dim3(256), 0, stream,
                        (const unsigned long long*)cand.data_ptr<int64_t>(),
                        (const unsigned*)ccount.data_ptr<int>(),
@@ -800,62 +795,6 @@ torch::Tensor ivf_route_probes(const torch::Tensor& queries,
 }
 
 }  // namespace
-
-std::tuple<torch::Tensor, torch::Tensor> ivf_scan_topk(
-    torch::Tensor queries, std::vector<torch::Tensor> segments,
-    torch::Tensor offsets, torch::Tensor ids, torch::Tensor probes, int64_t k,
-    int64_t valid_n, int64_t tail_lo, int64_t tail_hi, int64_t max_list_len) {
-  // Exact top-k of each query over the rows of its probed lists plus the
-  // tail [tail_lo, tail_hi). max_list_len only sizes the grid (any value
-  // >= 0 gives the same result); rows short of k candidates come back padded
-  // with (NEG_INF, -1), which the Python op normalises.
-  return ivf_scan_topk_impl(queries, segments, offsets, ids, probes, k, valid_n,
-                            tail_lo, tail_hi, max_list_len, nullptr);
-}
-
-std::tuple<torch::Tensor, torch::Tensor> ivf_scan_topk_filtered(
-    torch::Tensor queries, std::vector<torch::Tensor> segments,
-    std::vector<torch::Tensor> labels, torch::Tensor want, torch::Tensor offsets,
-    torch::Tensor ids, torch::Tensor probes, int64_t k, int64_t valid_n,
-    int64_t tail_lo, int64_t tail_hi, int64_t max_list_len) {
-  // ivf_scan_topk over the candidates row r with want[b] < 0 || label(r) ==
-  // want[b]; labels: one i32 tensor per segment, want: i32 [B].
-  const IvfFilter f = ivf_filter(segments, labels, want, queries);
-  return ivf_scan_topk_impl(queries, segments, offsets, ids, probes, k, valid_n,
-                            tail_lo, tail_hi, max_list_len, &f);
-}
-
-std::tuple<torch::Tensor, torch::Tensor> ivf_search(
-    torch::Tensor queries, std::vector<torch::Tensor> segments,
-    torch::Tensor centroids, torch::Tensor offsets, torch::Tensor ids,
-    int64_t nprobe, int64_t k, int64_t valid_n, int64_t n_indexed,
-    int64_t max_list_len) {
-  // route -> select -> scan: score the centroids, take the nprobe best
-  // lists per query (torch.topk on the tiny [B, L] score tensor), scan
-  // those lists plus the tail [n_indexed, valid_n) (empty when valid_n is
-  // a snapshot from before the index was built; listed ids >= valid_n are
-  // dropped by the scan).
-  auto probes = ivf_route_probes(queries, centroids, offsets, ids, nprobe, n_indexed);
-  return ivf_scan_topk(queries, std::move(segments), offsets, ids, probes, k,
-                       valid_n, std::min(n_indexed, valid_n), valid_n,
-                       max_list_len);
-}
-
-std::tuple<torch::Tensor, torch::Tensor> ivf_search_filtered(
-    torch::Tensor queries, std::vector<torch::Tensor> segments,
-    std::vector<torch::Tensor> labels, torch::Tensor want,
-    torch::Tensor centroids, torch::Tensor offsets, torch::Tensor ids,
-    int64_t nprobe, int64_t k, int64_t valid_n, int64_t n_indexed,
-    int64_t max_list_len) {
-  // ivf_search with the label predicate in the scan; the routing does not
-  // know labels. The filter is checked before the routing kernel runs.
-  ivf_filter(segments, labels, want, queries);
-  auto probes = ivf_route_probes(queries, centroids, offsets, ids, nprobe, n_indexed);
-  return ivf_scan_topk_filtered(queries, std::move(segments), std::move(labels),
-                                want, offsets, ids, probes, k, valid_n,
-                                std::min(n_indexed, valid_n), valid_n,
-                                max_list_len);
-}
 
 // ---- list-major (batched) routed scan --------------------------------------
 
@@ -904,13 +843,14 @@ std::vector<torch::Tensor> ivf_group_probes_op(torch::Tensor probes,
 namespace {
 
 // ivf_scan_topk_batched, and with a filter ivf_scan_topk_batched_filtered:
-// the same grouping, plan, candidate buffer and merge; only the scan kernel
-// differs.
+// the same grouping, plan, candidate buffer and merge; FILTER picks the
+// kernel's instantiation.
+template <bool FILTER>
 std::tuple<torch::Tensor, torch::Tensor> ivf_scan_topk_batched_impl(
     const torch::Tensor& queries, const std::vector<torch::Tensor>& segments,
     const torch::Tensor& offsets, const torch::Tensor& ids,
     const torch::Tensor& probes, int64_t k, int64_t valid_n, int64_t tail_lo,
-    int64_t tail_hi, int64_t max_list_len, const IvfFilter* filter) {
+    int64_t tail_hi, int64_t max_list_len, const IvfFilterArg<FILTER>& filter) {
   const IvfScanArgs a = ivf_scan_args(queries, segments, offsets, ids, probes, k,
                                       valid_n, tail_lo, tail_hi, max_list_len);
   const int B = a.B, D = a.D, L = a.L, nprobe = a.nprobe;
@@ -945,27 +885,16 @@ std::tuple<torch::Tensor, torch::Tensor> ivf_scan_topk_batched_impl(
     // grid.y holds at most 65535 tiles
     for (long t0 = 0; t0 < p.max_tiles; t0 += 65535) {
       const int nt = (int)std::min(p.max_tiles - t0, 65535L);
-      if (filter)
-        hipLaunchKernelGGL(
-            ivf_scan_grouped_filtered_kernel, dim3(p.slices, nt), dim3(256), lds,
-            stream, (const bf16_t*)queries.data_ptr() + (size_t)b0 * D, a.segs,
-            filter->labels, filter->want + b0,
-            (const long*)offsets.data_ptr<int64_t>(), ids.data_ptr<int>(),
-            grp[0].data_ptr<int>(), grp[1].data_ptr<int>(), tiles,
-            tiles + p.max_tiles, tiles + 2 * p.max_tiles, grp[3].data_ptr<int>(),
-            (int)t0, nb, nprobe + 1, L, (long)ids.size(0), D, (long)valid_n,
-            (long)tail_lo, (long)tail_hi, p.pairs,
-            (unsigned long long*)cand.data_ptr<int64_t>());
-      else
-        hipLaunchKernelGGL(
-            ivf_scan_grouped_kernel, dim3(p.slices, nt), dim3(256), lds, stream,
-            (const bf16_t*)queries.data_ptr() + (size_t)b0 * D, a.segs,
-            (const long*)offsets.data_ptr<int64_t>(), ids.data_ptr<int>(),
-            grp[0].data_ptr<int>(), grp[1].data_ptr<int>(), tiles,
-            tiles + p.max_tiles, tiles + 2 * p.max_tiles, grp[3].data_ptr<int>(),
-            (int)t0, nb, nprobe + 1, L, (long)ids.size(0), D, (long)valid_n,
-            (long)tail_lo, (long)tail_hi, p.pairs,
-            (unsigned long long*)cand.data_ptr<int64_t>());
+      hipLaunchKernelGGL(
+          ivf_scan_grouped_kernel<FILTER>, dim3(p.slices, nt), dim3(256), lds,
+          stream, (const bf16_t*)queries.data_ptr() + (size_t)b0 * D, a.segs,
+          ivf_filter_from(filter, b0),
+          (const long*)offsets.data_ptr<int64_t>(), ids.data_ptr<int>(),
+          grp[0].data_ptr<int>(), grp[1].data_ptr<int>(), tiles,
+          tiles + p.max_tiles, tiles + 2 * p.max_tiles, grp[3].data_ptr<int>(),
+          (int)t0, nb, nprobe + 1, L, (long)ids.size(0), D, (long)valid_n,
+          (long)tail_lo, (long)tail_hi, p.pairs,
+          (unsigned long long*)cand.data_ptr<int64_t>());
     }
     hipLaunchKernelGGL(emit_merge_topk, dim3(nb), dim3(256), 0, stream,
                        (const unsigned long long*)cand.data_ptr<int64_t>(),
@@ -977,7 +906,51 @@ std::tuple<torch::Tensor, torch::Tensor> ivf_scan_topk_batched_impl(
   return {out_score, out_idx};
 }
 
+// The four searches: route -> select -> scan. Score the centroids, take the
+// nprobe best lists per query, scan those lists plus the tail [n_indexed,
+// valid_n) (empty when valid_n is a snapshot from before the index was
+// built; listed ids >= valid_n are dropped by the scan). `batched` takes the
+// list-major scan (-> group -> scan -> merge). The routing does not know
+// labels; the caller has checked the filter before the routing kernel runs.
+template <bool FILTER>
+std::tuple<torch::Tensor, torch::Tensor> ivf_search_impl(
+    bool batched, const torch::Tensor& queries,
+    const std::vector<torch::Tensor>& segments, const IvfFilterArg<FILTER>& filter,
+    const torch::Tensor& centroids, const torch::Tensor& offsets,
+    const torch::Tensor& ids, int64_t nprobe, int64_t k, int64_t valid_n,
+    int64_t n_indexed, int64_t max_list_len) {
+  auto probes = ivf_route_probes(queries, centroids, offsets, ids, nprobe, n_indexed);
+  const auto scan =
+      batched ? ivf_scan_topk_batched_impl<FILTER> : ivf_scan_topk_impl<FILTER>;
+  return scan(queries, segments, offsets, ids, probes, k, valid_n,
+              std::min(n_indexed, valid_n), valid_n, max_list_len, filter);
+}
+
 }  // namespace
+
+std::tuple<torch::Tensor, torch::Tensor> ivf_scan_topk(
+    torch::Tensor queries, std::vector<torch::Tensor> segments,
+    torch::Tensor offsets, torch::Tensor ids, torch::Tensor probes, int64_t k,
+    int64_t valid_n, int64_t tail_lo, int64_t tail_hi, int64_t max_list_len) {
+  // Exact top-k of each query over the rows of its probed lists plus the
+  // tail [tail_lo, tail_hi). max_list_len only sizes the grid (any value
+  // >= 0 gives the same result); rows short of k candidates come back padded
+  // with (NEG_INF, -1), which the Python op normalises.
+  return ivf_scan_topk_impl<false>(queries, segments, offsets, ids, probes, k,
+                                   valid_n, tail_lo, tail_hi, max_list_len, {});
+}
+
+std::tuple<torch::Tensor, torch::Tensor> ivf_scan_topk_filtered(
+    torch::Tensor queries, std::vector<torch::Tensor> segments,
+    std::vector<torch::Tensor> labels, torch::Tensor want, torch::Tensor offsets,
+    torch::Tensor ids, torch::Tensor probes, int64_t k, int64_t valid_n,
+    int64_t tail_lo, int64_t tail_hi, int64_t max_list_len) {
+  // ivf_scan_topk over the candidates row r with want[b] < 0 || label(r) ==
+  // want[b]; labels: one i32 tensor per segment, want: i32 [B].
+  return ivf_scan_topk_impl<true>(queries, segments, offsets, ids, probes, k,
+                                  valid_n, tail_lo, tail_hi, max_list_len,
+                                  ivf_filter(segments, labels, want, queries));
+}
 
 std::tuple<torch::Tensor, torch::Tensor> ivf_scan_topk_batched(
     torch::Tensor queries, std::vector<torch::Tensor> segments,
@@ -986,9 +959,9 @@ std::tuple<torch::Tensor, torch::Tensor> ivf_scan_topk_batched(
   // ivf_scan_topk's contract through the list-major kernel: group the
   // (query, probe) pairs by list, scan every (tile, slice) once with
   // ivf_scan_grouped_kernel, finish with emit_merge_topk.
-  return ivf_scan_topk_batched_impl(queries, segments, offsets, ids, probes, k,
-                                    valid_n, tail_lo, tail_hi, max_list_len,
-                                    nullptr);
+  return ivf_scan_topk_batched_impl<false>(queries, segments, offsets, ids, probes,
+                                           k, valid_n, tail_lo, tail_hi,
+                                           max_list_len, {});
 }
 
 std::tuple<torch::Tensor, torch::Tensor> ivf_scan_topk_batched_filtered(
@@ -997,9 +970,39 @@ std::tuple<torch::Tensor, torch::Tensor> ivf_scan_topk_batched_filtered(
     torch::Tensor ids, torch::Tensor probes, int64_t k, int64_t valid_n,
     int64_t tail_lo, int64_t tail_hi, int64_t max_list_len) {
   // ivf_scan_topk_filtered's contract through the list-major kernel.
-  const IvfFilter f = ivf_filter(segments, labels, want, queries);
-  return ivf_scan_topk_batched_impl(queries, segments, offsets, ids, probes, k,
-                                    valid_n, tail_lo, tail_hi, max_list_len, &f);
+  return ivf_scan_topk_batched_impl<true>(
+      queries, segments, offsets, ids, probes, k, valid_n, tail_lo, tail_hi,
+      max_list_len, ivf_filter(segments, labels, want, queries));
+}
+
+std::tuple<torch::Tensor, torch::Tensor> ivf_search(
+    torch::Tensor queries, std::vector<torch::Tensor> segments,
+    torch::Tensor centroids, torch::Tensor offsets, torch::Tensor ids,
+    int64_t nprobe, int64_t k, int64_t valid_n, int64_t n_indexed,
+    int64_t max_list_len) {
+  return ivf_search_impl<false>(false, queries, segments, {}, centroids, offsets,
+                                ids, nprobe, k, valid_n, n_indexed, max_list_len);
+}
+
+std::tuple<torch::Tensor, torch::Tensor> ivf_search_batched(
+    torch::Tensor queries, std::vector<torch::Tensor> segments,
+    torch::Tensor centroids, torch::Tensor offsets, torch::Tensor ids,
+    int64_t nprobe, int64_t k, int64_t valid_n, int64_t n_indexed,
+    int64_t max_list_len) {
+  return ivf_search_impl<false>(true, queries, segments, {}, centroids, offsets,
+                                ids, nprobe, k, valid_n, n_indexed, max_list_len);
+}
+
+std::tuple<torch::Tensor, torch::Tensor> ivf_search_filtered(
+    torch::Tensor queries, std::vector<torch::Tensor> segments,
+    std::vector<torch::Tensor> labels, torch::Tensor want,
+    torch::Tensor centroids, torch::Tensor offsets, torch::Tensor ids,
+    int64_t nprobe, int64_t k, int64_t valid_n, int64_t n_indexed,
+    int64_t max_list_len) {
+  return ivf_search_impl<true>(false, queries, segments,
+                               ivf_filter(segments, labels, want, queries),
+                               centroids, offsets, ids, nprobe, k, valid_n,
+                               n_indexed, max_list_len);
 }
 
 std::tuple<torch::Tensor, torch::Tensor> ivf_search_batched_filtered(
@@ -1008,25 +1011,10 @@ std::tuple<torch::Tensor, torch::Tensor> ivf_search_batched_filtered(
     torch::Tensor centroids, torch::Tensor offsets, torch::Tensor ids,
     int64_t nprobe, int64_t k, int64_t valid_n, int64_t n_indexed,
     int64_t max_list_len) {
-  // ivf_search_filtered with the list-major scan.
-  ivf_filter(segments, labels, want, queries);
-  auto probes = ivf_route_probes(queries, centroids, offsets, ids, nprobe, n_indexed);
-  return ivf_scan_topk_batched_filtered(
-      queries, std::move(segments), std::move(labels), want, offsets, ids, probes,
-      k, valid_n, std::min(n_indexed, valid_n), valid_n, max_list_len);
-}
-
-std::tuple<torch::Tensor, torch::Tensor> ivf_search_batched(
-    torch::Tensor queries, std::vector<torch::Tensor> segments,
-    torch::Tensor centroids, torch::Tensor offsets, torch::Tensor ids,
-    int64_t nprobe, int64_t k, int64_t valid_n, int64_t n_indexed,
-    int64_t max_list_len) {
-  // ivf_search with the list-major scan: route -> select -> group -> scan
-  // -> merge (the last three inside ivf_scan_topk_batched).
-  auto probes = ivf_route_probes(queries, centroids, offsets, ids, nprobe, n_indexed);
-  return ivf_scan_topk_batched(queries, std::move(segments), offsets, ids, probes,
-                               k, valid_n, std::min(n_indexed, valid_n), valid_n,
-                               max_list_len);
+  return ivf_search_impl<true>(true, queries, segments,
+                               ivf_filter(segments, labels, want, queries),
+                               centroids, offsets, ids, nprobe, k, valid_n,
+                               n_indexed, max_list_len);
 }
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {

@@ -1,5 +1,5 @@
-"""GPU tests of the label-filtered routed scan: ivf_scan_topk_filtered_kernel
-(batched=False) and ivf_scan_grouped_filtered_kernel (batched=True) behind
+"""GPU tests of the label-filtered routed scan: ivf_scan_topk_kernel<true>
+(batched=False) and ivf_scan_grouped_kernel<true> (batched=True) behind
 ops.ivf_scan_topk_filtered / ops.ivf_search_filtered and
 EmbeddingStore.search(..., want=..., nprobe=..., route_filtered=True).
 

@@ -18,16 +18,26 @@ the tool prints `identical`, or a unified diff; a kernel's descriptor
 (.amdhsa_* directives) is compared apart from its instructions and changed
 directives are listed, next to the old and new .vgpr_count /
 .vgpr_spill_count / .private_segment_fixed_size / .group_segment_fixed_size
-metadata. Exit status is 1 when a symbol present in both listings differs
-in code.
+metadata. A symbol whose code differs also says whether the instructions per
+mnemonic are the same (`DIFFERS (same instruction mix, N)`: only operands,
+such as kernarg offsets and register numbers, or the order moved) or which
+counts changed (`DIFFERS (v_cndmask_b32 40->24; ...)`). Exit status is 1
+when a symbol present in both listings differs in code.
 
 --alias 'REGEX=REPL' rewrites symbol names (in both listings, everywhere)
 before matching, for a refactor that changes a mangled name on purpose, e.g.
 a dropped defaulted template parameter:
   --alias 'cosine_topk_partial_tILi(\\d+)ELi2EE=cosine_topk_partial_tILi\\1EE'
+or the routed scans, whose filtered twins became `template <bool FILTER>`
+instantiations (old name, then new name, onto one readable name):
+  --alias '_ZN7kakveda\\d+(ivf_scan_[a-z]+)_kernelE\\w+=\\1_kernel<false>'
+  --alias '_ZN7kakveda\\d+(ivf_scan_[a-z]+)_filtered_kernelE\\w+=\\1_kernel<true>'
+  --alias '_ZN7kakveda\\d+(ivf_scan_[a-z]+)_kernelILb0EEEv\\w+=\\1_kernel<false>'
+  --alias '_ZN7kakveda\\d+(ivf_scan_[a-z]+)_kernelILb1EEEv\\w+=\\1_kernel<true>'
 """
 
 import argparse
+import collections
 import difflib
 import re
 import sys
@@ -97,6 +107,12 @@ def parse(path, aliases):
     return funcs, order, meta
 
 
+def mix(code):
+    """Instructions per mnemonic of a normalised body (labels, directives out)."""
+    return collections.Counter(
+        l.split()[0] for l in code if not l.startswith(".") and not l.endswith(":"))
+
+
 def short(sym, width=64):
     """Readable name: strip the mangling prefix/suffix where it is obvious."""
     m = re.match(r"_ZN\d+[a-z_]+?(\d+)", sym)
@@ -139,7 +155,11 @@ def main():
             verdict = "identical"
         else:
             differs += 1
-            verdict = "DIFFERS"
+            omix, nmix = mix(ocode), mix(ncode)
+            moved = ["%s %d->%d" % (m, omix[m], nmix[m])
+                     for m in sorted(set(omix) | set(nmix)) if omix[m] != nmix[m]]
+            verdict = "DIFFERS (%s)" % ("; ".join(moved) if moved else
+                                        "same instruction mix, %d" % sum(nmix.values()))
             diff = list(difflib.unified_diff(ocode, ncode, "old", "new", lineterm="", n=2))
             print("=== %s: code differs (%d -> %d lines)" % (short(sym), len(ocode), len(ncode)))
             for line in diff[: args.max_diff_lines]:
