@@ -103,8 +103,9 @@ torch::Tensor new_rowthr(const KnnArgs& a) {
   return rowthr;
 }
 
-// Emission floors: a prepass over the first PRE_TILES*preg column tiles
-// writes a COMPACT [B][preg][KMAX] partial buffer of its own (so the floor
+// Emission floors: a prepass over the first pre_grid*pre_tiles column tiles
+// (the plan's sample, in the launch geometry of knn_plan.h prepass_geometry)
+// writes a COMPACT [B][pre_grid][KMAX] partial buffer of its own (so the floor
 // merge scans only what the prepass produced); topk_merge folds it into the
 // exact top-8 of the whole sampled column set, whose k-th (k <= KMAX, the
 // caller's floor depth: KMAX in production, any k from the debug probes)
@@ -115,17 +116,17 @@ struct Floors {
   torch::Tensor rowthr, samp_s, samp_i;
 };
 
-Floors run_emission_floors(const KnnArgs& a, int preg, int prepass_mode, int k,
-                           Filter flt = {}) {
+Floors run_emission_floors(const KnnArgs& a, int pre_grid, int pre_tiles,
+                           int prepass_mode, int k, Filter flt = {}) {
   Floors f{new_rowthr(a), torch::empty({(long)a.B, (long)KMAX}, a.f32()),
            torch::empty({(long)a.B, (long)KMAX}, a.i64())};
-  auto ppre_s = torch::empty({(long)a.B * preg * KMAX}, a.f32());
-  auto ppre_i = torch::empty({(long)a.B * preg * KMAX}, a.i32());
+  auto ppre_s = torch::empty({(long)a.B * pre_grid * KMAX}, a.f32());
+  auto ppre_i = torch::empty({(long)a.B * pre_grid * KMAX}, a.i32());
   // the prepass always runs the 128-row-tile kernel, also under the
   // 256-row-tile 8p main launch
-  launch_partial128(prepass_mode, dim3(preg, (a.B + BM - 1) / BM), a,
-                    ppre_s.data_ptr<float>(), ppre_i.data_ptr<int>(), PRE_TILES,
-                    preg, (unsigned*)f.rowthr.data_ptr<int>(), flt);
+  launch_partial128(prepass_mode, dim3(pre_grid, (a.B + BM - 1) / BM), a,
+                    ppre_s.data_ptr<float>(), ppre_i.data_ptr<int>(), pre_tiles,
+                    pre_grid, (unsigned*)f.rowthr.data_ptr<int>(), flt);
   // (filtered: the sample lists hold eligible columns only, so the floor
   // published below is the k-th best ELIGIBLE sampled score; with fewer
   // than k eligible samples that slot is still -inf, nothing is published
@@ -135,7 +136,7 @@ Floors run_emission_floors(const KnnArgs& a, int preg, int prepass_mode, int k,
   hipLaunchKernelGGL(topk_merge, dim3(a.B), dim3(THREADS), 0, a.stream,
                      ppre_s.data_ptr<float>(), ppre_i.data_ptr<int>(),
                      f.samp_s.data_ptr<float>(),
-                     (long*)f.samp_i.data_ptr<int64_t>(), preg, KMAX);
+                     (long*)f.samp_i.data_ptr<int64_t>(), pre_grid, KMAX);
   hipLaunchKernelGGL(publish_emission_floor, dim3((a.B + 255) / 256), dim3(256),
                      0, a.stream, f.samp_s.data_ptr<float>(),
                      (unsigned*)f.rowthr.data_ptr<int>(), a.B,
@@ -236,7 +237,8 @@ std::tuple<torch::Tensor, torch::Tensor> cosine_topk_impl(
     const int floor_k = KMAX;
     const Floors f =
         p.prepass
-            ? run_emission_floors(a, p.preg, p.prepass_mode, floor_k, flt)
+            ? run_emission_floors(a, p.pre_grid, p.pre_tiles, p.prepass_mode,
+                                  floor_k, flt)
             : Floors{new_rowthr(a), {}, {}};
     // The Emit8p main launch starts after the sampled columns
     // (p.skip_tiles, knn_plan.h main_geometry): the sample's top-KMAX are
@@ -286,6 +288,9 @@ std::tuple<torch::Tensor, torch::Tensor> cosine_topk_impl(
       printf("emit: rows=%d max=%ld mean=%.1f cap=%ld%s\n", B, mx,
              e.ccount.to(torch::kFloat32).mean().item<float>(), p.cap,
              mx > p.cap ? "  FALLBACK" : "");
+      if (p.prepass)
+        printf("emit: prepass pre_grid=%d pre_tiles=%d\n", p.pre_grid,
+               p.pre_tiles);
       if (p.mseg > 0)
         printf("emit: segments=%ld max=%d seg=%ld skip_tiles=%d\n",
                (long)e.esegcnt.size(0), e.esegcnt.max().item<int>(), p.mseg,
@@ -511,8 +516,23 @@ std::tuple<torch::Tensor, torch::Tensor> kmeans_update(
   return {sums, counts};
 }
 
+namespace {
+
+// The probes' floors: pregq sampled chunks in blocks of pre_tiles column
+// tiles (0: PRE_TILES, one block per chunk; any other value is checked like
+// KAKVEDA_KNN_PRE_TILES and refused before anything is launched).
+Floors probe_floors(const KnnArgs& a, int64_t pregq, int64_t pre_tiles, int k) {
+  const int preg = ((int)pregq) & ~7;
+  if (pre_tiles == 0) return run_emission_floors(a, preg, PRE_TILES, 11, k);
+  const int pre_grid = forced_pre_grid(preg, pre_tiles, "pre_tiles");
+  return run_emission_floors(a, pre_grid, (int)pre_tiles, 11, k);
+}
+
+}  // namespace
+
 std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> floor_probe(
-    torch::Tensor queries, torch::Tensor corpus, int64_t pregq, int64_t k) {
+    torch::Tensor queries, torch::Tensor corpus, int64_t pregq, int64_t k,
+    int64_t pre_tiles) {
   // Debug: run ONLY the emission floor pipeline (prepass -> compact
   // partials -> merge -> publish) and return (samp_s [B,KMAX], samp_i,
   // rowthr u32 [B]) for offline comparison against a torch reference. The
@@ -521,12 +541,13 @@ std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> floor_probe(
   check_bf16_2d(corpus, "corpus");
   const KnnArgs a = knn_args(queries, corpus, (int)corpus.size(0));
   TORCH_CHECK(k >= 1 && k <= KMAX, "k must be in [1,", KMAX, "]");
-  const Floors f = run_emission_floors(a, ((int)pregq) & ~7, 11, (int)k);
+  const Floors f = probe_floors(a, pregq, pre_tiles, (int)k);
   return {f.samp_s, f.samp_i, f.rowthr};
 }
 
 std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> emit_counts_probe(
-    torch::Tensor queries, torch::Tensor corpus, int64_t pregq, int64_t k) {
+    torch::Tensor queries, torch::Tensor corpus, int64_t pregq, int64_t k,
+    int64_t pre_tiles) {
   // Debug: run floors (k-th best of the sample) + the mode-9 emission
   // kernel + the binning step and return the raw per-row candidate counts
   // and candidates (no merge, no fallback) for offline inspection of which
@@ -535,7 +556,7 @@ std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> emit_counts_probe(
   check_bf16_2d(corpus, "corpus");
   const KnnArgs a = knn_args(queries, corpus, (int)corpus.size(0));
   TORCH_CHECK(k >= 1 && k <= KMAX, "k must be in [1,", KMAX, "]");
-  const Floors f = run_emission_floors(a, ((int)pregq) & ~7, 11, (int)k);
+  const Floors f = probe_floors(a, pregq, pre_tiles, (int)k);
   const Chunking ch = chunking(a.B, a.N, BM8, default_target(BM8));
   const long CAP = 32768;
   const long seg = emit_seg_cap(a.B, CAP, ch, 0);
@@ -1029,11 +1050,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("probe8p", &probe8p, "8p epilogue-isolation timing probe");
   m.def("floor_probe", &floor_probe, "emission floor pipeline debug probe",
         pybind11::arg("queries"), pybind11::arg("corpus"),
-        pybind11::arg("pregq"), pybind11::arg("k") = (int64_t)KMAX);
+        pybind11::arg("pregq"), pybind11::arg("k") = (int64_t)KMAX,
+        pybind11::arg("pre_tiles") = (int64_t)0);
   m.def("emit_counts_probe", &emit_counts_probe,
         "emission per-row count debug probe", pybind11::arg("queries"),
         pybind11::arg("corpus"), pybind11::arg("pregq"),
-        pybind11::arg("k") = (int64_t)KMAX);
+        pybind11::arg("k") = (int64_t)KMAX,
+        pybind11::arg("pre_tiles") = (int64_t)0);
   m.def("ivf_route_scores", &ivf_route_scores_op,
         "dense fp32 scores of queries against IVF centroids");
   m.def("ivf_scan_topk", &ivf_scan_topk,

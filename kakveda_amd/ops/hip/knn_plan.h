@@ -39,7 +39,16 @@ struct KnnEnv {
   long seg = 0;                  // KAKVEDA_KNN_EMIT_SEG (<= 0: default)
   bool emit_debug = false;       // KAKVEDA_KNN_EMIT_DEBUG=1
   bool skip_sample = true;       // KAKVEDA_KNN_SKIP_SAMPLE: 1 (default), 0
+  int pre_tiles = 0;             // KAKVEDA_KNN_PRE_TILES (0: the plan's rule)
 };
+
+// A forced size of the compact prepass's blocks, in column tiles (the
+// KAKVEDA_KNN_PRE_TILES knob and the probes' pre_tiles argument): a positive
+// multiple of PRE_TILES. Whether it divides a given sample is checked where
+// the sample is known (forced_pre_grid below).
+inline bool pre_tiles_wellformed(long t) {
+  return t >= PRE_TILES && t <= (1L << 24) && t % PRE_TILES == 0;
+}
 
 // `get` is std::getenv or anything with its signature.
 template <class GetEnv>
@@ -81,6 +90,22 @@ KnnEnv parse_knn_env(GetEnv&& get) {
                              "' is not a setting; accepted: 1 (default: the "
                              "emission main launch starts after the sampled "
                              "columns), 0 (it scans the whole corpus)");
+  v = get("KAKVEDA_KNN_PRE_TILES");
+  const std::string pt = v ? v : "";
+  if (!pt.empty()) {
+    char* end = nullptr;
+    const long t = std::strtol(pt.c_str(), &end, 10);
+    if (pt.find_first_not_of("0123456789") != std::string::npos ||
+        pt.size() > 8 || *end != '\0' || !pre_tiles_wellformed(t))
+      throw std::runtime_error(
+          "KAKVEDA_KNN_PRE_TILES='" + pt +
+          "' is not a setting; accepted: a positive multiple of " +
+          std::to_string(PRE_TILES) +
+          " (column tiles per block of the emission prepass; " +
+          std::to_string(PRE_TILES) +
+          " is one block per sampled chunk), or unset for the plan's rule");
+    e.pre_tiles = (int)t;
+  }
   return e;
 }
 
@@ -153,6 +178,12 @@ struct KnnPlan {
   int skip_tiles;  // leading BN8-column tiles left to the prepass sample
   Chunking mch;    // chunking of the other ntiles - skip_tiles tiles
   long mseg;       // records per block segment of that launch
+  // The prepass as it is launched (prepass_geometry below): pre_grid blocks
+  // per row tile of pre_tiles column tiles each, over the same sample:
+  // pre_grid * pre_tiles == preg * PRE_TILES. preg x PRE_TILES unless the
+  // prepass is the compact one.
+  int pre_grid;
+  int pre_tiles;
 };
 
 // Makespan model of an 8-phase main launch, in column tiles per CU. The
@@ -234,6 +265,70 @@ inline void main_geometry(KnnPlan& p, int B, const KnnEnv& env) {
   p.mseg = emit_seg_cap(B, env.cap, p.mch, env.seg);
 }
 
+// Blocks of the 128x128 kernel resident at once: 2 per CU (its 80 KiB of
+// LDS), 256 CUs.
+constexpr int PREPASS_ROUND = 2 * 256;
+
+// grid.x of a compact prepass forced to `pre_tiles` column tiles per block
+// over a sample of preg * PRE_TILES tiles. The size must be well formed,
+// divide the sample, and leave a grid that is a multiple of 8 (the in-kernel
+// XCD remap is bijective only then) unless it is PRE_TILES itself, the
+// launch of one block per sampled chunk.
+inline int forced_pre_grid(int preg, long pre_tiles, const char* what) {
+  const long total = (long)preg * PRE_TILES;
+  if (pre_tiles_wellformed(pre_tiles) && total % pre_tiles == 0 &&
+      (pre_tiles == PRE_TILES || (total / pre_tiles) % 8 == 0))
+    return (int)(total / pre_tiles);
+  throw std::runtime_error(
+      std::string(what) + "=" + std::to_string(pre_tiles) +
+      " does not fit this request's prepass sample of " +
+      std::to_string(total) + " column tiles; accepted: a multiple of " +
+      std::to_string(PRE_TILES) +
+      " that divides the sample into a multiple of 8 blocks per row tile (" +
+      std::to_string(PRE_TILES) + " always fits)");
+}
+
+// Launch geometry of the prepass. The sample is preg * PRE_TILES column
+// tiles whatever the geometry; a column's score depends only on the K order
+// inside its tile, so the sample's exact top-KMAX is the same under any
+// split of the sample into blocks.
+// Every block bootstraps private top-KMAX lists from empty, through the
+// serial insert path, before its thresholds prune anything: a streaming
+// top-8 over n columns takes about 8 (1 + ln(n / 8)) inserts, so per query
+// row 256 blocks of 8 tiles pay ~21,000 inserts where 32 blocks of 64 tiles
+// pay ~3,700. The result needs one top-8 of the sample per row, so the
+// COMPACT prepass (the emission floors: it writes a buffer of its own with
+// stride pre_grid, and the floor merge shrinks with it) runs the longest
+// blocks, in doublings of PRE_TILES, that still
+//   - divide the sample,
+//   - leave grid.x a multiple of 8 (the in-kernel XCD remap),
+//   - fill one whole round of resident blocks (PREPASS_ROUND) with
+//     pre_grid * ceil(B / BM) blocks.
+// Where no longer block qualifies (B <= 8 serving, B = 256, every filtered
+// small-batch plan) the geometry is preg x PRE_TILES. The warming prepass of
+// the list path always is: it writes the main launch's [row][chunk_id]
+// partial slots. KAKVEDA_KNN_PRE_TILES forces the compact prepass's size
+// (forced_pre_grid: a request it does not fit is refused) and acts on
+// nothing else. No field above these two changes with any of this.
+inline void prepass_geometry(KnnPlan& p, int B, const KnnEnv& env) {
+  p.pre_grid = p.preg;
+  p.pre_tiles = PRE_TILES;
+  if (!p.prepass_compact) return;
+  if (env.pre_tiles > 0) {
+    p.pre_grid = forced_pre_grid(p.preg, env.pre_tiles, "KAKVEDA_KNN_PRE_TILES");
+    p.pre_tiles = env.pre_tiles;
+    return;
+  }
+  const long total = (long)p.preg * PRE_TILES;
+  const long row_tiles = ((long)B + BM - 1) / BM;
+  for (long t = 2 * PRE_TILES; total % t == 0; t *= 2) {
+    const long g = total / t;
+    if (g % 8 != 0 || g * row_tiles < PREPASS_ROUND) break;
+    p.pre_grid = (int)g;
+    p.pre_tiles = (int)t;
+  }
+}
+
 // Every main launch and every prepass puts its row tiles on grid.y, which
 // the device limits to MAX_GRID_Y blocks. The prepass runs the 128-row-tile
 // kernel under either main tile, so it needs ceil(B / BM) rows of blocks
@@ -279,6 +374,7 @@ inline KnnPlan plan_cosine_topk_filtered(int B, int N, int k, const KnnEnv& env,
             : p.ch.nchunks * KMAX <= 1024 ? MergeKernel::Small
                                           : MergeKernel::Merge;
   main_geometry(p, B, env);  // skips nothing: no 8-phase kernel here
+  prepass_geometry(p, B, env);
   return p;
 }
 
@@ -354,6 +450,7 @@ inline KnnPlan plan_cosine_topk(int B, int N, int k, const KnnEnv& env,
             : p.ch.nchunks * KMAX <= 1024    ? MergeKernel::Small
                                              : MergeKernel::Merge;
   main_geometry(p, B, env);
+  prepass_geometry(p, B, env);
   return p;
 }
 
