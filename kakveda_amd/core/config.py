@@ -31,6 +31,8 @@ DEFAULT_CONFIG: Dict[str, Any] = {
         "top_k": 5,
         "hash_dim": 1 << 16,
         "encoder_seed": 1234,
+        # hash signature texts with the device featurizer; host is the default
+        "device_featurize": False,
         # optional cluster-routed (approximate) match; exact is the default
         "routed": {
             "enabled": False,

@@ -93,3 +93,31 @@ def featurize_batch(
         idx_out[b, : len(idxs)] = idxs
         w_out[b, : len(ws)] = ws
     return idx_out, w_out
+
+
+def pack_texts(texts: Sequence[str]) -> Tuple[np.ndarray, np.ndarray, List[int]]:
+    """Pack texts for the device featurizer (``ops.featurize_bytes``).
+
+    Returns (uint8 array of every text's bytes back to back, int32 offsets
+    [B+1], host_rows). ``host_rows`` lists the rows the host must featurise
+    itself, packed here as empty texts: texts that are not ``str.isascii()``
+    (``str.lower()`` can map a non-ASCII character into the token class,
+    which a byte tokeniser cannot follow) and texts longer than
+    ``ops.FEATURIZE_MAX_BYTES``.
+    """
+    from kakveda_amd.ops import FEATURIZE_MAX_BYTES
+
+    host_rows = [
+        i for i, t in enumerate(texts) if len(t) > FEATURIZE_MAX_BYTES or not t.isascii()
+    ]
+    if host_rows:
+        texts = list(texts)
+        for i in host_rows:
+            texts[i] = ""
+    offsets = np.zeros(len(texts) + 1, dtype=np.int64)
+    np.cumsum(np.fromiter(map(len, texts), dtype=np.int64, count=len(texts)), out=offsets[1:])
+    if offsets[-1] >= 1 << 31:
+        raise ValueError("texts of one batch must stay below 2^31 bytes together")
+    # ASCII only from here on: one byte per character
+    buf = np.frombuffer(bytearray("".join(texts), "ascii"), dtype=np.uint8)
+    return buf, offsets.astype(np.int32), host_rows

@@ -14,11 +14,19 @@ the same math in plain torch (deterministic, used by BASELINE config 1).
 
 from __future__ import annotations
 
-from typing import Sequence
+from typing import Optional, Sequence, Tuple
 
 import torch
 
-from kakveda_amd.encoder.featurizer import featurize_batch
+from kakveda_amd.encoder.featurizer import featurize_batch, pack_texts
+
+#: batch size from which ``device_featurize=True`` hashes on a CUDA device
+#: (None would mean never: the flag inert). Measured,
+#: profiles/device_featurize.md: the smallest B from which the device arm of
+#: encode_texts beats the host arm by more than the spread between rounds is
+#: the smallest measured, 1 (0.139 against 0.151 ms, both arms within 0.9%;
+#: 24x at 64 texts, 370x at 2,048)
+DEVICE_FEATURIZE_MIN_B: Optional[int] = 1
 
 
 class TraceEncoder:
@@ -30,12 +38,19 @@ class TraceEncoder:
         device: str = "cpu",
         depth: int = 2,
         max_features: int = 64,
+        device_featurize: bool = False,
     ):
         self.dim = dim
         self.hash_dim = hash_dim
         self.seed = seed
         self.max_features = max_features
         self.device = torch.device(device)
+        #: hash the texts with ops.featurize_bytes instead of featurize_batch
+        #: (off by default). On a CUDA device that is the HIP kernel, from
+        #: DEVICE_FEATURIZE_MIN_B texts on; on a CPU device the reference op.
+        self.device_featurize = device_featurize
+        #: rows the device featurizer handed back to featurize_batch so far
+        self.host_fallbacks = 0
 
         gen = torch.Generator(device="cpu").manual_seed(seed)
         # Hashed-feature embedding table, scaled so bag outputs are O(1).
@@ -56,6 +71,8 @@ class TraceEncoder:
     @torch.no_grad()
     def encode_texts(self, texts: Sequence[str]) -> torch.Tensor:
         """Encode signature texts -> [B, dim] unit-norm float32 embeddings."""
+        if self._featurize_on_device(len(texts)):
+            return self.encode_features(*self._featurize_device(texts))
         idx, w = featurize_batch(
             texts, hash_dim=self.hash_dim, seed=0, max_features=self.max_features
         )
@@ -63,6 +80,45 @@ class TraceEncoder:
             torch.from_numpy(idx).to(self.device),
             torch.from_numpy(w).to(self.device),
         )
+
+    def _featurize_on_device(self, n_texts: int) -> bool:
+        if not self.device_featurize or n_texts == 0 or self.max_features > 128:
+            return False
+        if self.device.type != "cuda":
+            return True  # the reference op: the same plumbing without a GPU
+        return DEVICE_FEATURIZE_MIN_B is not None and n_texts >= DEVICE_FEATURIZE_MIN_B
+
+    def _featurize_device(self, texts: Sequence[str]) -> Tuple[torch.Tensor, torch.Tensor]:
+        """``featurize_batch`` through ``ops.featurize_bytes``: pack, upload,
+        hash on the device, then redo on the host the rows the device could
+        not take (``pack_texts``'s host rows and the rows it flagged). One
+        integer comes back from the device when nothing was flagged."""
+        from kakveda_amd import ops
+
+        buf, offsets, host_rows = pack_texts(texts)
+        idx, w, status, flagged = ops.featurize_bytes(
+            torch.from_numpy(buf).to(self.device),
+            torch.from_numpy(offsets).to(self.device),
+            self.hash_dim,
+            0,
+            self.max_features,
+        )
+        redo = list(host_rows)
+        if int(flagged.item()) > 0:
+            # host rows were packed empty (status 0): no row is listed twice
+            redo += torch.nonzero(status).flatten().tolist()
+        if redo:
+            hidx, hw = featurize_batch(
+                [texts[i] for i in redo],
+                hash_dim=self.hash_dim,
+                seed=0,
+                max_features=self.max_features,
+            )
+            rows = torch.tensor(redo, dtype=torch.int64, device=self.device)
+            idx[rows] = torch.from_numpy(hidx).to(self.device)
+            w[rows] = torch.from_numpy(hw).to(self.device)
+            self.host_fallbacks += len(redo)
+        return idx, w
 
     @torch.no_grad()
     def encode_features(self, idx: torch.Tensor, w: torch.Tensor) -> torch.Tensor:

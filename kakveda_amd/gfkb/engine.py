@@ -547,6 +547,7 @@ class GfkbEngine:
         top_k: int = 5,
         nprobe: Optional[int] = None,
         route_filtered: bool = False,
+        device_featurize: bool = False,
     ):
         self.data_dir = Path(data_dir)
         self.data_dir.mkdir(parents=True, exist_ok=True)
@@ -562,7 +563,15 @@ class GfkbEngine:
         self.route_filtered = route_filtered
         self._lock = threading.RLock()
 
-        self.encoder = TraceEncoder(dim=dim, hash_dim=hash_dim, seed=encoder_seed, device=device)
+        # device_featurize: hash signature texts with the device featurizer
+        # (TraceEncoder.device_featurize); off by default
+        self.encoder = TraceEncoder(
+            dim=dim,
+            hash_dim=hash_dim,
+            seed=encoder_seed,
+            device=device,
+            device_featurize=device_featurize,
+        )
         self.store = EmbeddingStore(dim, device=device, capacity=1024)
         self.sidecar = EmbeddingSidecar(
             self.data_dir / "embeddings.bin", dim, self.store.dtype

@@ -28,6 +28,10 @@ Kernels (kakveda_amd/ops/hip/):
   label predicate of cosine_topk_filtered inside either scan (the
   ``FILTER`` instantiation of the same kernel template), so a filter-first
   request can stay routed.
+- featurize_bytes — the optional device featurizer: signature-text bytes to
+  the padded index/weight rows of encoder.featurizer.featurize_batch, one
+  wave per text (tokenise by ballot, FNV-1a per token, two LDS bitonic
+  sorts); rows it cannot take are flagged for the host.
 
 Policy: on a CUDA(ROCm) device the HIP extension is REQUIRED — ops raise
 if it is missing rather than silently falling back to eager PyTorch. The
@@ -257,6 +261,104 @@ def embedding_bag(table: torch.Tensor, idx: torch.Tensor, w: torch.Tensor) -> to
     live = (ix >= 0) & (ix < table.shape[0])
     flat = table[ix.clamp(0, table.shape[0] - 1).reshape(-1)].reshape(*idx.shape, table.shape[1]).float()
     return (flat * (w.float() * live).unsqueeze(-1)).sum(dim=1)
+
+
+# ---------------------------------------------------------------------------
+# device featurizer (signature-text bytes -> hashed n-gram rows)
+# ---------------------------------------------------------------------------
+
+#: capacity of one text on the device (mirror of featurize_plan.h; pinned by
+#: tests/test_device_featurize.py): bytes, and uni+bigrams before
+#: de-duplication. A text over either gets status 1 and a zero row.
+FEATURIZE_MAX_BYTES = 1024
+FEATURIZE_MAX_GRAMS = 256
+
+#: row status of featurize_bytes
+FEATURIZE_OK = 0
+FEATURIZE_TOO_MANY_GRAMS = 1  # over FEATURIZE_MAX_BYTES or FEATURIZE_MAX_GRAMS
+FEATURIZE_TOO_MANY_FEATURES = 2  # more than max_features buckets
+
+_HIGH_TO_SPACE = bytes(range(128)) + b" " * 128
+
+
+def featurize_start_state(seed: int) -> int:
+    """Start state of every gram hash for ``seed`` (featurizer._fnv1a)."""
+    from kakveda_amd.encoder.featurizer import _FNV_OFFSET, _MASK64
+
+    return (_FNV_OFFSET ^ (seed * 0x9E3779B97F4A7C15)) & _MASK64
+
+
+def featurize_bytes(
+    buf: torch.Tensor, offsets: torch.Tensor, hash_dim: int, seed: int, max_features: int
+) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """``featurize_batch`` over texts given as bytes.
+
+    buf: uint8, every text back to back with nothing between them; offsets:
+    int32 [B+1], text b being ``buf[offsets[b]:offsets[b+1]]``. ``hash_dim``
+    in [1, 2^31), ``max_features`` in [1, 128] (``embedding_bag``'s limit).
+    Returns (idx i32 [B, max_features], w f32 [B, max_features], status i32
+    [B], flagged i32 [1]): the rows ``featurize_batch`` gives for the decoded
+    texts - indices equal, weights to fp32 rounding - where status is 0.
+    Status 1 marks a text over FEATURIZE_MAX_BYTES bytes or
+    FEATURIZE_MAX_GRAMS grams, status 2 one with more than ``max_features``
+    buckets (``featurize_batch`` then keeps the largest by an unstable sort,
+    which cannot be reproduced): such a row is all zeros and the caller
+    recomputes it on the host. ``flagged`` is the number of such rows.
+
+    Bytes are tokenised as ASCII: the result equals ``featurize_batch`` only
+    for texts that are ``str.isascii()`` (``featurizer.pack_texts`` routes
+    the others to the host).
+    """
+    hash_dim, max_features = int(hash_dim), int(max_features)
+    if not 1 <= hash_dim < 1 << 31:
+        raise ValueError(f"hash_dim must be in [1, 2^31), got {hash_dim}")
+    if not 1 <= max_features <= 128:
+        raise ValueError(f"max_features must be in [1, 128], got {max_features}")
+    if buf.device.type == "cuda":
+        ext = _require_ext()
+        idx, w, status, flagged = ext.featurize_bytes(
+            buf, offsets, hash_dim, featurize_start_state(int(seed)), max_features
+        )
+        return idx, w, status, flagged
+    return featurize_bytes_ref(buf, offsets, hash_dim, seed, max_features)
+
+
+def featurize_bytes_ref(
+    buf: torch.Tensor, offsets: torch.Tensor, hash_dim: int, seed: int, max_features: int
+) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Reference of ``featurize_bytes`` on the host: decode each text, set
+    the status by the kernel's rules, and take the rows from
+    ``featurize_batch``. A flagged row is all zeros, as from the kernel."""
+    import numpy as np
+
+    from kakveda_amd.encoder.featurizer import featurize, featurize_batch, tokenize
+
+    raw = buf.detach().cpu().numpy().tobytes()
+    off = [int(o) for o in offsets.detach().cpu().tolist()]
+    B = len(off) - 1
+    status = np.zeros(B, dtype=np.int32)
+    texts = []
+    for b in range(B):
+        lo, hi = off[b], off[b + 1]
+        if not 0 <= lo <= hi <= len(raw):
+            raise ValueError(f"offsets of text {b} ({lo}, {hi}) lie outside the buffer")
+        # latin-1 keeps one character per byte; bytes >= 0x80 are separators
+        # on the device, so they become spaces before the str tokeniser
+        # (whose lower() could turn them into token characters) sees them
+        text = raw[lo:hi].translate(_HIGH_TO_SPACE).decode("ascii")
+        n_tok = len(tokenize(text))
+        if hi - lo > FEATURIZE_MAX_BYTES or 2 * n_tok - 1 > FEATURIZE_MAX_GRAMS:
+            status[b] = FEATURIZE_TOO_MANY_GRAMS
+        elif len(featurize(text, hash_dim=hash_dim, seed=seed)[0]) > max_features:
+            status[b] = FEATURIZE_TOO_MANY_FEATURES
+        texts.append(text if status[b] == FEATURIZE_OK else "")
+    idx, w = featurize_batch(texts, hash_dim=hash_dim, seed=seed, max_features=max_features)
+    return (
+        torch.from_numpy(idx),
+        torch.from_numpy(w),
+        torch.from_numpy(status),
+        torch.tensor([int((status != 0).sum())], dtype=torch.int32),
+    )
 
 
 # ---------------------------------------------------------------------------

@@ -9,6 +9,7 @@
 #include "kernels_impl.h"
 #include "ivf_impl.h"
 #include "ivf_batch_impl.h"
+#include "featurize_impl.h"
 
 using namespace kakveda;
 
@@ -1038,6 +1039,50 @@ std::tuple<torch::Tensor, torch::Tensor> ivf_search_batched_filtered(
                                n_indexed, max_list_len);
 }
 
+// ---- device featurizer ------------------------------------------------------
+
+std::vector<torch::Tensor> featurize_bytes(torch::Tensor buf, torch::Tensor offsets,
+                                           int64_t hash_dim, uint64_t start_state,
+                                           int64_t max_features) {
+  // Signature texts as bytes (all texts back to back in `buf`, text b being
+  // buf[offsets[b]:offsets[b+1]]) -> {idx i32 [B, max_features], w f32
+  // [B, max_features], status i32 [B], flagged i32 [1]}: the rows of
+  // featurize_batch (featurize_plan.h states the contract), a zero row and
+  // a non-zero status where a text is over capacity or has more than
+  // max_features buckets, and the number of such rows.
+  TORCH_CHECK(buf.is_cuda() && buf.scalar_type() == torch::kUInt8 &&
+                  buf.dim() == 1 && buf.is_contiguous(),
+              "buf must be contiguous 1-D u8 on GPU");
+  TORCH_CHECK(offsets.is_cuda() && offsets.scalar_type() == torch::kInt32 &&
+                  offsets.dim() == 1 && offsets.is_contiguous() &&
+                  offsets.size(0) >= 1 && offsets.device() == buf.device(),
+              "offsets must be contiguous 1-D i32 with B+1 entries on buf's device");
+  TORCH_CHECK(hash_dim >= 1 && hash_dim < (int64_t)1 << 31,
+              "hash_dim must be in [1, 2^31)");
+  TORCH_CHECK(max_features >= 1 && max_features <= FEATURIZE_MAX_FEATURES,
+              "max_features must be in [1,", FEATURIZE_MAX_FEATURES, "]");
+  const int64_t B = offsets.size(0) - 1;
+  auto i32 = torch::TensorOptions().dtype(torch::kInt32).device(buf.device());
+  auto f32 = torch::TensorOptions().dtype(torch::kFloat32).device(buf.device());
+  auto idx = torch::empty({B, max_features}, i32);
+  auto w = torch::empty({B, max_features}, f32);
+  auto status = torch::empty({B}, i32);
+  auto flagged = torch::zeros({1}, i32);
+  if (B == 0) return {idx, w, status, flagged};  // nothing to launch
+  const int64_t blocks =
+      (B + FEATURIZE_TEXTS_PER_BLOCK - 1) / FEATURIZE_TEXTS_PER_BLOCK;
+  hipLaunchKernelGGL(featurize_bytes_kernel, dim3((unsigned)blocks),
+                     dim3(64 * FEATURIZE_TEXTS_PER_BLOCK), 0,
+                     c10::hip::getCurrentHIPStream().stream(),
+                     (const unsigned char*)buf.data_ptr(), (long)buf.size(0),
+                     offsets.data_ptr<int>(), (int)B, (unsigned)hash_dim,
+                     (unsigned long long)start_state, (int)max_features,
+                     idx.data_ptr<int>(), w.data_ptr<float>(),
+                     status.data_ptr<int>(), flagged.data_ptr<int>());
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+  return {idx, w, status, flagged};
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("cosine_topk", &cosine_topk, "fused cosine top-k (MFMA + LDS top-k)");
   m.def("cosine_topk_filtered", &cosine_topk_filtered,
@@ -1119,6 +1164,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("ids"), pybind11::arg("nprobe"), pybind11::arg("k"),
         pybind11::arg("valid_n"), pybind11::arg("n_indexed"),
         pybind11::arg("max_list_len") = (int64_t)0);
+  m.def("featurize_bytes", &featurize_bytes,
+        "hash signature-text bytes into padded n-gram feature rows",
+        pybind11::arg("buf"), pybind11::arg("offsets"), pybind11::arg("hash_dim"),
+        pybind11::arg("start_state"), pybind11::arg("max_features"));
+  m.attr("FEATURIZE_MAX_BYTES") = FEATURIZE_MAX_BYTES;
+  m.attr("FEATURIZE_MAX_GRAMS") = FEATURIZE_MAX_GRAMS;
+  m.attr("FEATURIZE_TEXTS_PER_BLOCK") = FEATURIZE_TEXTS_PER_BLOCK;
   m.attr("KMAX") = KMAX;
   m.attr("IVF_BATCH_QTILE") = IVF_BATCH_QTILE;
   m.attr("IVF_BATCH_MAX_D") = IVF_BATCH_MAX_D;

@@ -167,6 +167,19 @@ def _setup_routed(engine: GfkbEngine, config: Optional[Any]) -> None:
     )
 
 
+def _setup_featurize(engine: GfkbEngine, config: Optional[Any]) -> None:
+    """Apply ``gfkb.device_featurize``: true turns the engine's encoder over
+    to the device featurizer. False (the default) touches nothing, so an
+    engine built with the flag keeps it."""
+    if config is None:
+        from kakveda_amd.core.config import ConfigStore
+
+        config = ConfigStore()
+    if bool(config.get("gfkb.device_featurize", False)):
+        engine.encoder.device_featurize = True
+        logger.info("device featurizer on")
+
+
 def create_app(
     data_dir: Optional[str] = None,
     device: Optional[str] = None,
@@ -174,7 +187,8 @@ def create_app(
     config: Optional[Any] = None,
 ) -> FastAPI:
     """``config`` is a ``ConfigStore`` (or anything with its ``get``); its
-    ``gfkb.routed`` block opts the service into routed search."""
+    ``gfkb.routed`` block opts the service into routed search, its
+    ``gfkb.device_featurize`` flag into hashing texts on the device."""
     app = FastAPI(title="Kakveda-AMD GFKB")
     if engine is None:
         import torch
@@ -185,6 +199,7 @@ def create_app(
         )
     app.state.engine = engine
     _setup_routed(engine, config)
+    _setup_featurize(engine, config)
     # micro-batcher on by default; KAKVEDA_MATCH_BATCHER=0 opts out
     batcher = (
         MatchBatcher(engine)
