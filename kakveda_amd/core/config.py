@@ -33,6 +33,9 @@ DEFAULT_CONFIG: Dict[str, Any] = {
         "encoder_seed": 1234,
         # hash signature texts with the device featurizer; host is the default
         "device_featurize": False,
+        # keep an int8 mirror of the rows for exact small-batch matches
+        # (+50.5% store memory at D=768); off is the default
+        "int8_mirror": False,
         # optional cluster-routed (approximate) match; exact is the default
         "routed": {
             "enabled": False,

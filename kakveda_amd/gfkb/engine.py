@@ -47,6 +47,9 @@ logger = logging.getLogger(__name__)
 #: tail rows / indexed rows past which a routed store asks for a rebuild
 STALE_WARN_FRACTION = 0.10
 
+#: rows per quantiser call when a filled store builds its int8 mirror
+MIRROR_CHUNK_ROWS = 1 << 20
+
 
 class EmbeddingStore:
     """A growable, segmented [N, D] row store on a device; rows are unit
@@ -71,6 +74,13 @@ class EmbeddingStore:
     with the rows. ``search(..., want=...)`` restricts each query to the
     rows of one label inside the scan (``ops.cosine_topk_filtered``).
 
+    Optional int8 mirror (``int8_mirror=True`` or ``enable_mirror()``): per
+    segment an int8 copy of the rows with one (scale, error bound) pair per
+    row, created, grown, split and adopted with the rows as the labels are.
+    Exact searches of up to ``ops.Q8_MAX_B`` queries scan it instead of the
+    bf16 rows and rescore the survivors from them (``ops.cosine_topk_q8``):
+    the same answer from about half the bytes. The routed scans stay bf16.
+
     Optional routed search: ``build_index()`` attaches an ``IvfIndex``
     (gfkb/ivf.py) and ``search(..., nprobe=n)`` then scans only the n best
     inverted lists per query plus the tail of rows appended since the build.
@@ -87,6 +97,7 @@ class EmbeddingStore:
         device: str = "cpu",
         capacity: int = 1024,
         segment_rows: Optional[int] = None,
+        int8_mirror: bool = False,
     ):
         self.dim = dim
         self.device = torch.device(device)
@@ -109,6 +120,55 @@ class EmbeddingStore:
         self._stale_warned = False
         #: filtered queries a routed filtered search handed to the exact fill
         self.exact_fills = 0
+        #: the optional int8 mirror (ops.quantize_rows_q8): one codes and one
+        #: meta tensor per segment, empty lists while it is off
+        self.int8_mirror = False
+        self._codes: List[torch.Tensor] = []
+        self._meta: List[torch.Tensor] = []
+        if int8_mirror:
+            self.enable_mirror()
+
+    # -- int8 mirror ---------------------------------------------------------
+
+    def _new_mirror(self, n: int) -> Tuple[torch.Tensor, torch.Tensor]:
+        return ops.new_q8_mirror(n, self.dim, self.device)
+
+    def _quantize(self, seg_no: int, lo: int, hi: int) -> None:
+        """Quantise rows [lo, hi) of segment ``seg_no`` into its mirror, in
+        chunks of at most MIRROR_CHUNK_ROWS rows."""
+        seg = self._segments[seg_no]
+        for a in range(lo, hi, MIRROR_CHUNK_ROWS):
+            b = min(a + MIRROR_CHUNK_ROWS, hi)
+            ops.quantize_rows_q8(seg[a:b], self._codes[seg_no], self._meta[seg_no], a)
+
+    def enable_mirror(self) -> None:
+        """Turn the int8 mirror on: allocate it beside every segment and
+        quantise the live rows. From then on ``append`` keeps it current and
+        exact small-batch searches read it (``ops.cosine_topk_q8``). It costs
+        (D + 8) / (2 D) of the rows' memory on a GPU store."""
+        if self.int8_mirror:
+            return
+        pairs = [self._new_mirror(int(seg.shape[0])) for seg in self._segments]
+        self._codes = [c for c, _m in pairs]
+        self._meta = [m for _c, m in pairs]
+        for i, (_seg, valid, _base) in enumerate(self._live_segments()):
+            self._quantize(i, 0, valid)
+        self.int8_mirror = True
+
+    def mirror_range(self, start: int, end: int) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(codes, meta) of rows [start, end), each as one tensor."""
+        if not self.int8_mirror:
+            raise RuntimeError("the store has no int8 mirror: call enable_mirror()")
+        end = min(end, self.count)
+        cs, ms = [], []
+        for i, (_seg, valid, base) in enumerate(self._live_segments()):
+            lo, hi = max(start - base, 0), min(end - base, valid)
+            if lo < hi:
+                cs.append(self._codes[i][lo:hi])
+                ms.append(self._meta[i][lo:hi])
+        if not cs:
+            return self._codes[0][:0], self._meta[0][:0]
+        return torch.cat(cs, dim=0), torch.cat(ms, dim=0)
 
     def _new_labels(self, n: int) -> torch.Tensor:
         return torch.full((n,), -1, dtype=torch.int32, device=self.device)
@@ -149,6 +209,11 @@ class EmbeddingStore:
                 labels = self._new_labels(cap)
                 labels[: self.count] = self._labels[0][: self.count]
                 self._labels[0] = labels
+                if self.int8_mirror:
+                    codes, meta = self._new_mirror(cap)
+                    codes[: self.count] = self._codes[0][: self.count]
+                    meta[: self.count] = self._meta[0][: self.count]
+                    self._codes[0], self._meta[0] = codes, meta
             else:
                 # at scale: copy-free growth by a fixed segment quantum
                 self._segments.append(
@@ -157,6 +222,10 @@ class EmbeddingStore:
                     )
                 )
                 self._labels.append(self._new_labels(self.segment_rows))
+                if self.int8_mirror:
+                    codes, meta = self._new_mirror(self.segment_rows)
+                    self._codes.append(codes)
+                    self._meta.append(meta)
 
     def adopt(self, data: torch.Tensor, labels: Optional[torch.Tensor] = None) -> None:
         """Take ownership of a pre-built [n, D] row tensor (zero copy) —
@@ -176,6 +245,10 @@ class EmbeddingStore:
         self._label_counts = {}
         self._count_labels(labels, n)
         self.index = None  # it described the rows just replaced
+        if self.int8_mirror:
+            codes, meta = self._new_mirror(n)
+            self._codes, self._meta = [codes], [meta]
+            self._quantize(0, 0, n)
 
     def append(self, rows: torch.Tensor, labels: Optional[torch.Tensor] = None) -> int:
         """Append [n, D] rows (splitting across segments); returns the
@@ -192,12 +265,16 @@ class EmbeddingStore:
         first = self.count
         written = 0
         base = 0
-        for seg, lab in zip(self._segments, self._labels):
+        for seg_no, (seg, lab) in enumerate(zip(self._segments, self._labels)):
             seg_rows = int(seg.shape[0])
             if self.count + written < base + seg_rows and written < n:
                 off = self.count + written - base
                 take = min(seg_rows - off, n - written)
                 seg[off : off + take] = rows[written : written + take].to(self.dtype)
+                # the mirror of exactly these rows, before count is bumped:
+                # rows below count are immutable in both copies
+                if self.int8_mirror:
+                    self._quantize(seg_no, off, off + take)
                 # slots past the live prefix are -1 already (never reused)
                 if labels is not None:
                     lab[off : off + take] = labels[written : written + take]
@@ -402,17 +479,26 @@ class EmbeddingStore:
         segs = self._live_segments(count)
         w = None if want is None else want.to(device=self.device, dtype=torch.int32)
 
-        def topk(seg: torch.Tensor, labels: torch.Tensor, n: int):
+        # exact from here on; small batches read the int8 mirror when it is on
+        q8 = self.int8_mirror and q.shape[0] <= ops.Q8_MAX_B
+
+        def topk(seg_no: int, n: int):
+            seg, labels = self._segments[seg_no], self._labels[seg_no]
+            if q8:
+                return ops.cosine_topk_q8(
+                    q, seg, self._codes[seg_no], self._meta[seg_no], k, valid_n=n,
+                    labels=None if w is None else labels, want=w,
+                )
             if w is None:
                 return ops.cosine_topk(q, seg, k, valid_n=n)
             return ops.cosine_topk_filtered(q, seg, labels, w, k, valid_n=n)
 
         if len(segs) <= 1:
-            return topk(self._segments[0], self._labels[0], count)
+            return topk(0, count)
         parts_s, parts_i = [], []
         # the live segments are a prefix of _segments, so labels line up
-        for (seg, valid, base), labels in zip(segs, self._labels):
-            s, i = topk(seg, labels, valid)
+        for seg_no, (seg, valid, base) in enumerate(segs):
+            s, i = topk(seg_no, valid)
             parts_i.append(torch.where(i < 0, i, i + base))
             parts_s.append(s)
         all_s = torch.cat(parts_s, dim=1)
@@ -548,6 +634,7 @@ class GfkbEngine:
         nprobe: Optional[int] = None,
         route_filtered: bool = False,
         device_featurize: bool = False,
+        int8_mirror: bool = False,
     ):
         self.data_dir = Path(data_dir)
         self.data_dir.mkdir(parents=True, exist_ok=True)
@@ -572,7 +659,13 @@ class GfkbEngine:
             device=device,
             device_featurize=device_featurize,
         )
-        self.store = EmbeddingStore(dim, device=device, capacity=1024)
+        #: keep an int8 mirror of the rows for exact small-batch searches
+        #: (EmbeddingStore.enable_mirror); rebuilt from the rows on restart,
+        #: never persisted
+        self.int8_mirror = int8_mirror
+        self.store = EmbeddingStore(
+            dim, device=device, capacity=1024, int8_mirror=int8_mirror
+        )
         self.sidecar = EmbeddingSidecar(
             self.data_dir / "embeddings.bin", dim, self.store.dtype
         )
@@ -636,7 +729,14 @@ class GfkbEngine:
         store) and reload every known identity into it, preserving row
         order (sidecar fast path, re-encode fallback). Must happen before
         serving begins."""
+        if self.int8_mirror and not isinstance(new_store, EmbeddingStore):
+            raise NotImplementedError(
+                f"int8_mirror is not supported on {type(new_store).__name__}: "
+                "sharded and distributed stores keep no mirror"
+            )
         with self._lock:
+            if self.int8_mirror:
+                new_store.enable_mirror()
             self.store = new_store
             if self._row_identity:
                 self._restore_rows(self._row_identity)

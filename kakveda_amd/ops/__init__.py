@@ -9,6 +9,11 @@ Kernels (kakveda_amd/ops/hip/):
 - cosine_topk_filtered — the same search with a per-query label predicate
   pushed into the scan (filtered instantiations of the 128x128 list kernel
   and of the streaming small-batch kernel; exact at any selectivity).
+- quantize_rows_q8 / cosine_topk_q8 — the optional int8 row mirror: per-row
+  symmetric int8 codes with the row's scale and an upper bound of its
+  quantisation error, and the exact small-batch search that scans the codes
+  (half the bytes), adds the error as a margin and rescores the survivors
+  from the bf16 rows (ops/hip/q8_plan.h, q8_impl.h).
 - l2normalize_ — in-place row L2-normalisation (bf16, vectorised loads).
 - embedding_bag — weighted gather-sum over the hashed-feature table
   (the trace-encoder front end).
@@ -222,6 +227,267 @@ def cosine_topk_filtered_ref(
         scores = torch.cat([scores, pad_s], dim=1)
         idx = torch.cat([idx, pad_i], dim=1)
     return scores.float(), idx.long()
+
+
+# ---------------------------------------------------------------------------
+# int8 row mirror: quantiser and the two-stage exact small-batch search
+# ---------------------------------------------------------------------------
+
+#: codes per 128-byte segment of a mirror row; D must be a multiple of it
+#: (mirror of q8_plan.h Q8_SEG)
+Q8_SEG = 128
+#: rows with a smaller amax are stored as zeros (q8_plan.h Q8_MIN_AMAX)
+_Q8_MIN_AMAX = 2.0 ** -100
+#: additive part of the stored error and of qn (q8_plan.h Q8_ERR_ABS)
+_Q8_ERR_ABS = 2.0 ** -50
+#: candidates per query of the emission path (knn_plan.h KnnEnv.cap)
+_Q8_CAP = 32768
+
+#: Largest batch at which ``EmbeddingStore.search`` takes the int8 mirror: the
+#: largest B at which the q8 arm of benchmarks/q8_scan_bench.py beat the bf16
+#: arm by more than both arms' spread in every cell (profiles/q8_mirror.md:
+#: D=768, k=5, mixture and isotropic corpus, unfiltered and a 10% label). At
+#: 10M rows it wins at every B (1.43-1.48x at B=1, 1.27-1.33x at 2,
+#: 1.11-1.12x at 4, 1.06-1.09x at 8); at 1M rows 1.09-1.10x, 1.06-1.07x and
+#: 1.02-1.03x (spread <= 0.7%) at B=1, 2, 4, and 0.99-1.00x at B=8: a loss.
+Q8_MAX_B = 4
+
+#: batches that overflowed the candidate buffer of the q8 path and were
+#: answered by the bf16 search instead (a process-wide counter)
+q8_overflow_fallbacks = 0
+
+
+def _q8_check_dim(D: int) -> None:
+    if D < Q8_SEG or D % Q8_SEG != 0:
+        raise ValueError(
+            f"the int8 mirror needs D to be a multiple of {Q8_SEG}, got D = {D}"
+        )
+
+
+def _q8_roundup(D: int) -> float:
+    """Factor that rounds an fp32 norm of D terms up past its real value
+    (derived in q8_plan.h)."""
+    return 1.0 + (D + 16) * 2.0 ** -24
+
+
+def quantize_rows_q8_ref(
+    rows: torch.Tensor, out_codes: torch.Tensor, out_meta: torch.Tensor, first_row: int = 0
+) -> None:
+    """Reference of ``quantize_rows_q8`` in torch, to the contract of
+    q8_plan.h: per row ``amax = max|c_i|``, ``scale = amax / 127`` and
+    ``inv = 127 / amax`` in fp32, ``n_i = clamp(round_half_even(c_i * inv),
+    -127, 127)`` from one fp32 multiply, and ``err >= ||c - scale * n||``
+    (here: the float64 norm, rounded up by the kernel's factor). Codes and
+    scales are bit-equal to the kernel's; ``err`` obeys the same bound."""
+    n, D = int(rows.shape[0]), int(rows.shape[1])
+    _q8_check_dim(D)
+    if n == 0:
+        return
+    x = rows.detach().float().cpu()
+    amax = x.abs().amax(dim=1)
+    amax = torch.where(torch.isnan(amax), torch.zeros_like(amax), amax)
+    livef = amax >= _Q8_MIN_AMAX
+    safe = torch.where(livef, amax, torch.ones_like(amax))
+    # tensor / tensor: a Python scalar on the left would be computed as
+    # reciprocal(safe) * 127, two roundings where the contract has one
+    c127 = torch.full_like(safe, 127.0)
+    scale = torch.where(livef, safe / c127, torch.zeros_like(amax))
+    inv = torch.where(livef, c127 / safe, torch.zeros_like(amax))
+    codes = torch.round(x * inv[:, None]).clamp_(-127.0, 127.0)
+    codes = torch.where(torch.isnan(codes), torch.zeros_like(codes), codes)
+    resid = (x.double() - scale.double()[:, None] * codes.double()).norm(dim=1)
+    err = torch.where(
+        livef,
+        resid * _q8_roundup(D) + _Q8_ERR_ABS,
+        amax.double() * (D ** 0.5) * _q8_roundup(D) * (1.0 + 2.0 ** -20),
+    )
+    # the cast rounds to nearest: step up where it landed below
+    err32 = err.float()
+    err32 = torch.where(err32.double() < err, torch.nextafter(err32, err32.new_tensor(float("inf"))), err32)
+    sl = slice(int(first_row), int(first_row) + n)
+    out_codes[sl] = codes.to(torch.int8).to(out_codes.device)
+    out_meta[sl] = torch.stack([scale, err32], dim=1).to(out_meta.device)
+
+
+def quantize_rows_q8(
+    rows: torch.Tensor, out_codes: torch.Tensor, out_meta: torch.Tensor, first_row: int = 0
+) -> None:
+    """Quantise ``rows`` [n, D] into the int8 mirror: codes int8 go to
+    ``out_codes[first_row : first_row + n]`` ([*, D]) and (scale, err) fp32
+    pairs to ``out_meta[first_row : first_row + n]`` ([*, 2]), where
+    ``scale * codes`` approximates the row and ``err`` is an upper bound of
+    the L2 norm of what it misses (contract: ops/hip/q8_plan.h). D must be a
+    multiple of Q8_SEG. GPU: a HIP kernel over bf16 rows; CPU: the reference."""
+    _q8_check_dim(int(rows.shape[1]))
+    if rows.device.type == "cuda":
+        _require_ext().quantize_rows_q8(rows.contiguous(), out_codes, out_meta, int(first_row))
+        return
+    quantize_rows_q8_ref(rows, out_codes, out_meta, first_row)
+
+
+def new_q8_mirror(n: int, D: int, device) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Empty mirror tensors for ``n`` rows: (codes int8 [n, D], meta f32 [n, 2])."""
+    _q8_check_dim(int(D))
+    return (
+        torch.zeros(n, D, dtype=torch.int8, device=device),
+        torch.zeros(n, 2, dtype=torch.float32, device=device),
+    )
+
+
+def q8_in_plan(B: int, N: int, k: int, filtered: bool) -> bool:
+    """Whether the default dispatch plan (knn_plan.h plan_cosine_topk) gives
+    this request to the streaming small-batch kernel, which is where
+    ``cosine_topk_q8`` scans the mirror: N >= 65,536 and B <= 8, and k > 1 on
+    the unfiltered table."""
+    return N >= 65536 and B <= 8 and (filtered or k > 1)
+
+
+def _q8_sample_rows(N: int, filtered: bool) -> int:
+    """Rows the emission prepass of a B <= 8 request samples under the
+    default plan (knn_plan.h: preg sampled chunks of PRE_TILES 128-column
+    tiles), for the reference's floors."""
+    tile, target = (128, 2048) if filtered else (256, 512)
+    ntiles = -(-N // tile)
+    chunk_tiles = max(4, min(-(-ntiles // target), 128))
+    nchunks = (-(-ntiles // chunk_tiles) + 7) & ~7
+    preg = min(256, nchunks) & ~7
+    return min(N, preg * 8 * 128)
+
+
+def q8_scores_ref(queries: torch.Tensor, codes: torch.Tensor, meta: torch.Tensor) -> torch.Tensor:
+    """fp32 stage-1 scores ``scale_r * sum_i q_i n_i`` of every (query, row)."""
+    return (queries.float() @ codes.float().t()) * meta[:, 0][None, :]
+
+
+def q8_emit_mask_ref(
+    queries: torch.Tensor,
+    corpus: torch.Tensor,
+    codes: torch.Tensor,
+    meta: torch.Tensor,
+    valid_n: int,
+    labels: Optional[torch.Tensor] = None,
+    want: Optional[torch.Tensor] = None,
+    margin: bool = True,
+) -> torch.Tensor:
+    """Stages 0 and 1 of ``cosine_topk_q8_ref``: bool [B, valid_n], the rows
+    emitted for each query. Stage 0: the floor of query b is the 8th best
+    fp32 score over the eligible rows among the first ``_q8_sample_rows``
+    (none with fewer than 8), lowered by D * 2^-22. Stage 1: row r is emitted
+    iff it is eligible and ``scale_r * q.n_r + qn_b * err_r + D * 2^-22 >=
+    floor``. ``margin=False`` drops the ``qn * err`` term: the broken search
+    the tests show the planted input to catch."""
+    n = int(valid_n)
+    D = int(queries.shape[1])
+    q = queries.float()
+    filtered = want is not None
+    elig = torch.ones(q.shape[0], n, dtype=torch.bool, device=q.device)
+    if filtered:
+        w = want.to(q.device).long()[:, None]
+        elig = (w < 0) | (labels[:n].to(q.device).long()[None, :] == w)
+    ns = _q8_sample_rows(n, filtered)
+    samp = (q @ corpus[:ns].float().t()).masked_fill(~elig[:, :ns], float("-inf"))
+    kth = torch.topk(samp, min(KMAX, ns), dim=1).values[:, -1] if ns >= KMAX else samp.new_full(
+        (q.shape[0],), float("-inf"))
+    slack = D * 2.0 ** -22
+    floor = kth - slack
+    s8 = q8_scores_ref(q, codes[:n], meta[:n])
+    if margin:
+        qn = (q.double().norm(dim=1) * _q8_roundup(D) + _Q8_ERR_ABS).float()
+        s8 = s8 + qn[:, None] * meta[:n, 1][None, :]
+    return elig & (s8 + slack >= floor[:, None])
+
+
+def cosine_topk_q8_ref(
+    queries: torch.Tensor,
+    corpus: torch.Tensor,
+    codes: torch.Tensor,
+    meta: torch.Tensor,
+    k: int,
+    valid_n: Optional[int] = None,
+    labels: Optional[torch.Tensor] = None,
+    want: Optional[torch.Tensor] = None,
+) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``cosine_topk_q8`` in torch (fp32 accumulate): floors from the sampled
+    rows, emission from the int8 mirror with each row's error margin
+    (``q8_emit_mask_ref``), exact scores of the emitted rows from ``corpus``,
+    top-k of those. A query with more than the candidate buffer's capacity
+    of emitted rows sends the batch to the plain reference search and bumps
+    ``q8_overflow_fallbacks``, as on the GPU. Requests outside
+    ``q8_in_plan`` run the plain reference search."""
+    global q8_overflow_fallbacks
+    n = int(valid_n) if valid_n is not None else corpus.shape[0]
+    B = queries.shape[0]
+    _q8_check_dim(int(queries.shape[1]))
+    filtered = want is not None
+
+    def plain():
+        if filtered:
+            return cosine_topk_filtered_ref(queries, corpus, labels, want, k, n)
+        return cosine_topk_ref(queries, corpus, k, n)
+
+    if n <= 0 or not q8_in_plan(B, n, min(int(k), KMAX), filtered):
+        return plain()
+    mask = q8_emit_mask_ref(queries, corpus, codes, meta, n, labels, want)
+    if int(mask.sum(dim=1).max()) > _Q8_CAP:
+        q8_overflow_fallbacks += 1
+        return plain()
+    sims = (queries.float() @ corpus[:n].float().t()).masked_fill(~mask, float("-inf"))
+    kk = min(k, n)
+    scores, idx = torch.topk(sims, kk, dim=1)
+    idx = torch.where(torch.isinf(scores) & (scores < 0), torch.full_like(idx, -1), idx)
+    return _pad_topk(scores.float(), idx.long(), k)
+
+
+def cosine_topk_q8(
+    queries: torch.Tensor,
+    corpus: torch.Tensor,
+    codes: torch.Tensor,
+    meta: torch.Tensor,
+    k: int,
+    valid_n: Optional[int] = None,
+    labels: Optional[torch.Tensor] = None,
+    want: Optional[torch.Tensor] = None,
+) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``cosine_topk`` (``cosine_topk_filtered`` when ``labels``/``want`` are
+    given) that reads the int8 mirror of the corpus where the request is one
+    of the streaming small-batch kernel's (``q8_in_plan``): the scan over all
+    rows reads ``codes``/``meta`` (``quantize_rows_q8`` of ``corpus``: D + 8
+    bytes a row against 2D), emits every row whose int8 score plus its known
+    quantisation error could reach the emission floor, and the emitted rows
+    are scored again from the bf16 ``corpus``. The result is exact - the
+    candidates are a superset of the bf16 scan's and carry its scores. Every
+    other request runs the bf16 search unchanged, and so does a batch whose
+    candidates overflow their buffer (``q8_overflow_fallbacks`` counts them).
+    Shapes, padding and the KMAX clamp as ``cosine_topk``/``_filtered``; D
+    must be a multiple of Q8_SEG."""
+    global q8_overflow_fallbacks
+    _q8_check_dim(int(queries.shape[1]))
+    if (labels is None) != (want is None):
+        raise ValueError("labels and want go together")
+    n = int(valid_n) if valid_n is not None else corpus.shape[0]
+    B = queries.shape[0]
+    if n <= 0:
+        return (
+            torch.full((B, k), float("-inf"), dtype=torch.float32, device=queries.device),
+            torch.full((B, k), -1, dtype=torch.int64, device=queries.device),
+        )
+    if queries.device.type != "cuda":
+        return cosine_topk_q8_ref(queries, corpus, codes, meta, k, n, labels, want)
+    ext = _require_ext()
+    kk = min(int(k), KMAX)
+    filt = {}
+    if want is not None:
+        filt = dict(
+            labels=labels.to(device=corpus.device, dtype=torch.int32).contiguous(),
+            want=want.to(device=queries.device, dtype=torch.int32).contiguous(),
+        )
+    scores, idx, overflowed, _counts = ext.cosine_topk_q8(
+        queries, corpus, codes, meta, kk, n, **filt
+    )
+    q8_overflow_fallbacks += int(overflowed)
+    if want is not None:
+        scores = torch.where(idx < 0, torch.full_like(scores, float("-inf")), scores)
+    return _pad_topk(scores, idx, k)
 
 
 # ---------------------------------------------------------------------------

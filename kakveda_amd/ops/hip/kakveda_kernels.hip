@@ -10,6 +10,7 @@
 #include "ivf_impl.h"
 #include "ivf_batch_impl.h"
 #include "featurize_impl.h"
+#include "q8_impl.h"
 
 using namespace kakveda;
 
@@ -397,6 +398,178 @@ std::tuple<torch::Tensor, torch::Tensor> cosine_topk_filtered(
   static const KnnEnv env = parse_knn_env(std::getenv);
   return cosine_topk_impl(queries, corpus, (int)k, N, env, true,
                           Filter{labels.data_ptr<int>(), want.data_ptr<int>()});
+}
+
+// ---------------------------------------------------------------------------
+// int8 row mirror (q8_plan.h, q8_impl.h)
+// ---------------------------------------------------------------------------
+namespace {
+
+void check_q8_mirror(const torch::Tensor& codes, const torch::Tensor& meta,
+                     const torch::Device& dev, int64_t rows, int64_t D) {
+  TORCH_CHECK(q8_dim_ok(D), "the int8 mirror needs D to be a multiple of ",
+              Q8_SEG, " (below 2^20), got D = ", D);
+  TORCH_CHECK(codes.is_cuda() && codes.device() == dev &&
+                  codes.scalar_type() == torch::kInt8 && codes.dim() == 2 &&
+                  codes.is_contiguous() && codes.size(1) == D &&
+                  codes.size(0) >= rows,
+              "codes must be contiguous int8 [>= ", rows, ", ", D,
+              "] on the rows' device");
+  TORCH_CHECK(meta.is_cuda() && meta.device() == dev &&
+                  meta.scalar_type() == torch::kFloat32 && meta.dim() == 2 &&
+                  meta.is_contiguous() && meta.size(1) == 2 &&
+                  meta.size(0) >= rows,
+              "meta must be contiguous fp32 [>= ", rows, ", 2] on the rows' device");
+}
+
+// Stage 1 of the q8 search into e.cand / e.ccount.
+void launch_q8_emit(const KnnArgs& a, const KnnPlan& p, const torch::Tensor& codes,
+                    const torch::Tensor& meta, const Floors& f, EmitBufs& e,
+                    Filter flt) {
+  const size_t lds = (size_t)a.B * a.D * sizeof(float);
+  TORCH_CHECK(lds <= 64 * 1024, "cosine_topk_q8: ", a.B, " fp32 queries of D = ",
+              a.D, " do not fit the kernel's 64 KiB of LDS");
+  const auto kernel = flt ? q8_emit_kernel<true> : q8_emit_kernel<false>;
+  hipLaunchKernelGGL(kernel, dim3(p.smallb_blocks), dim3(256), lds, a.stream,
+                     a.q, (const signed char*)codes.data_ptr<int8_t>(),
+                     meta.data_ptr<float>(), a.B, (long)a.N, a.D,
+                     (const unsigned*)f.rowthr.data_ptr<int>(),
+                     (unsigned long long*)e.cand.data_ptr<int64_t>(),
+                     (unsigned*)e.ccount.data_ptr<int>(), p.cap, flt.labels,
+                     flt.want);
+}
+
+struct Q8Checked {
+  int N;
+  Filter flt;
+};
+
+Q8Checked check_q8_search(const torch::Tensor& queries, const torch::Tensor& corpus,
+                          const torch::Tensor& codes, const torch::Tensor& meta,
+                          int64_t k, int64_t valid_n,
+                          const c10::optional<torch::Tensor>& labels,
+                          const c10::optional<torch::Tensor>& want) {
+  check_bf16_2d(queries, "queries");
+  check_bf16_2d(corpus, "corpus");
+  const int D = queries.size(1);
+  const int N = (int)valid_n;
+  TORCH_CHECK(corpus.size(1) == D, "dim mismatch");
+  TORCH_CHECK(N >= 1 && N <= corpus.size(0), "valid_n out of range");
+  TORCH_CHECK(k >= 1 && k <= KMAX, "k must be in [1,", KMAX, "]");
+  check_q8_mirror(codes, meta, corpus.device(), N, D);
+  TORCH_CHECK(labels.has_value() == want.has_value(),
+              "labels and want go together");
+  Filter flt;
+  if (labels) {
+    const torch::Tensor& l = *labels;
+    const torch::Tensor& w = *want;
+    TORCH_CHECK(l.is_cuda() && l.device() == corpus.device() &&
+                    l.scalar_type() == torch::kInt32 && l.dim() == 1 &&
+                    l.is_contiguous() && l.size(0) >= N,
+                "labels must be contiguous 1-D i32 on the corpus device with at "
+                "least valid_n entries");
+    TORCH_CHECK(w.is_cuda() && w.device() == queries.device() &&
+                    w.scalar_type() == torch::kInt32 && w.dim() == 1 &&
+                    w.is_contiguous() && w.size(0) == queries.size(0),
+                "want must be contiguous 1-D i32 on the query device with one "
+                "entry per query row");
+    flt = Filter{l.data_ptr<int>(), w.data_ptr<int>()};
+  }
+  return {N, flt};
+}
+
+}  // namespace
+
+void quantize_rows_q8(torch::Tensor rows, torch::Tensor out_codes,
+                      torch::Tensor out_meta, int64_t first_row) {
+  check_bf16_2d(rows, "rows");
+  const int64_t n = rows.size(0), D = rows.size(1);
+  TORCH_CHECK(first_row >= 0, "first_row must be >= 0");
+  check_q8_mirror(out_codes, out_meta, rows.device(), first_row + n, D);
+  if (n == 0) return;
+  const int blocks = (int)std::min((n + 31) / 32, (int64_t)8192);
+  hipLaunchKernelGGL(q8_quantize_kernel, dim3(blocks), dim3(256), 0,
+                     c10::hip::getCurrentHIPStream().stream(),
+                     (const bf16_t*)rows.data_ptr(), (long)n, (int)D,
+                     (signed char*)out_codes.data_ptr<int8_t>(),
+                     out_meta.data_ptr<float>(), (long)first_row);
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+}
+
+// The two-stage exact search over the mirror. Where the plan of the request
+// selects the streaming small-batch kernel, stage 1 scans the int8 codes
+// (q8_emit_kernel), stage 2 rescores the candidates from the bf16 rows
+// (q8_rescore), and the existing merge and overflow check follow; every other
+// request, and an overflowed one, is answered by cosine_topk_impl as it is.
+// Returns (scores, idx, overflowed, counts): overflowed is 1 when the batch
+// fell back, counts the per-query stage-1 candidate counts (empty off-plan).
+std::tuple<torch::Tensor, torch::Tensor, int64_t, torch::Tensor> cosine_topk_q8(
+    torch::Tensor queries, torch::Tensor corpus, torch::Tensor codes,
+    torch::Tensor meta, int64_t k, int64_t valid_n,
+    c10::optional<torch::Tensor> labels, c10::optional<torch::Tensor> want) {
+  const Q8Checked c =
+      check_q8_search(queries, corpus, codes, meta, k, valid_n, labels, want);
+  TORCH_CHECK(queries.size(1) % BK == 0, "D must be a multiple of ", BK);
+  static const KnnEnv env = parse_knn_env(std::getenv);
+  const KnnArgs a = knn_args(queries, corpus, c.N);
+  const KnnPlan p = plan_cosine_topk(a.B, c.N, (int)k, env, true, (bool)c.flt);
+  if (p.main != MainKernel::SmallB || p.merge != MergeKernel::Emit) {
+    auto [s, i] = cosine_topk_impl(queries, corpus, (int)k, c.N, env, true, c.flt);
+    return {s, i, 0, torch::empty({0}, a.i32())};
+  }
+  const Floors f =
+      p.prepass ? run_emission_floors(a, p.pre_grid, p.pre_tiles, p.prepass_mode,
+                                      KMAX, c.flt)
+                : Floors{new_rowthr(a), {}, {}};
+  EmitBufs e = new_emit_bufs(a, p.cap, p.mch);
+  launch_q8_emit(a, p, codes, meta, f, e, c.flt);
+  hipLaunchKernelGGL(q8_rescore, dim3(64, a.B), dim3(256), 0, a.stream, a.q, a.c,
+                     a.D, (unsigned long long*)e.cand.data_ptr<int64_t>(),
+                     (const unsigned*)e.ccount.data_ptr<int>(), p.cap);
+  auto out_score = torch::empty({a.B, k}, a.f32());
+  auto out_idx = torch::empty({a.B, k}, a.i64());
+  hipLaunchKernelGGL(emit_merge_topk, dim3(a.B), dim3(256), 0, a.stream,
+                     (const unsigned long long*)e.cand.data_ptr<int64_t>(),
+                     (const unsigned*)e.ccount.data_ptr<int>(),
+                     out_score.data_ptr<float>(),
+                     (long*)out_idx.data_ptr<int64_t>(), a.B, p.cap, (int)k);
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+  const long mx = (long)e.ccount.max().item<int>();
+  if (mx > p.cap) {
+    auto [s, i] = cosine_topk_impl(queries, corpus, (int)k, c.N, env, true, c.flt);
+    return {s, i, 1, e.ccount};
+  }
+  return {out_score, out_idx, 0, e.ccount};
+}
+
+// Benchmark probe: the stage-1 candidate counts of one request under both
+// arms, from one set of floors: (q8 counts, bf16 counts), i32 [B] each. The
+// request must be one the q8 path takes.
+std::tuple<torch::Tensor, torch::Tensor> q8_counts_probe(
+    torch::Tensor queries, torch::Tensor corpus, torch::Tensor codes,
+    torch::Tensor meta, int64_t k, int64_t valid_n,
+    c10::optional<torch::Tensor> labels, c10::optional<torch::Tensor> want) {
+  const Q8Checked c =
+      check_q8_search(queries, corpus, codes, meta, k, valid_n, labels, want);
+  static const KnnEnv env = parse_knn_env(std::getenv);
+  const KnnArgs a = knn_args(queries, corpus, c.N);
+  const KnnPlan p = plan_cosine_topk(a.B, c.N, (int)k, env, true, (bool)c.flt);
+  TORCH_CHECK(p.main == MainKernel::SmallB && p.prepass,
+              "q8_counts_probe: not a request of the small-batch plan");
+  const Floors f = run_emission_floors(a, p.pre_grid, p.pre_tiles,
+                                       p.prepass_mode, KMAX, c.flt);
+  EmitBufs e8 = new_emit_bufs(a, p.cap, p.mch);
+  launch_q8_emit(a, p, codes, meta, f, e8, c.flt);
+  EmitBufs e16 = new_emit_bufs(a, p.cap, p.mch);
+  const auto v4 = c.flt ? smallb_emit_kernel_v4<true> : smallb_emit_kernel_v4<false>;
+  hipLaunchKernelGGL(v4, dim3(p.smallb_blocks), dim3(256), (size_t)a.B * a.D * 2,
+                     a.stream, a.q, a.c, a.B, (long)a.N, a.D,
+                     (const unsigned*)f.rowthr.data_ptr<int>(),
+                     (unsigned long long*)e16.cand.data_ptr<int64_t>(),
+                     (unsigned*)e16.ccount.data_ptr<int>(), p.cap, c.flt.labels,
+                     c.flt.want);
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+  return {e8.ccount, e16.ccount};
 }
 
 void l2normalize_(torch::Tensor t, int64_t start_row, int64_t end_row) {
@@ -1087,6 +1260,20 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("cosine_topk", &cosine_topk, "fused cosine top-k (MFMA + LDS top-k)");
   m.def("cosine_topk_filtered", &cosine_topk_filtered,
         "cosine top-k over the corpus rows whose label matches each query's");
+  m.def("quantize_rows_q8", &quantize_rows_q8,
+        "quantise bf16 rows into the int8 mirror (codes, (scale, err))");
+  m.def("cosine_topk_q8", &cosine_topk_q8,
+        "exact small-batch top-k: int8 mirror scan + bf16 rescore",
+        pybind11::arg("queries"), pybind11::arg("corpus"), pybind11::arg("codes"),
+        pybind11::arg("meta"), pybind11::arg("k"), pybind11::arg("valid_n"),
+        pybind11::arg("labels") = pybind11::none(),
+        pybind11::arg("want") = pybind11::none());
+  m.def("q8_counts_probe", &q8_counts_probe,
+        "stage-1 candidate counts of the int8 and the bf16 arm",
+        pybind11::arg("queries"), pybind11::arg("corpus"), pybind11::arg("codes"),
+        pybind11::arg("meta"), pybind11::arg("k"), pybind11::arg("valid_n"),
+        pybind11::arg("labels") = pybind11::none(),
+        pybind11::arg("want") = pybind11::none());
   m.def("l2normalize_", &l2normalize_, "in-place row L2 normalisation");
   m.def("embedding_bag", &embedding_bag, "weighted embedding bag");
   m.def("kmeans_update", &kmeans_update, "segmented centroid sum + counts");

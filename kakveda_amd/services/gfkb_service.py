@@ -178,6 +178,18 @@ def _setup_featurize(engine: GfkbEngine, config: Optional[Any]) -> None:
     if bool(config.get("gfkb.device_featurize", False)):
         engine.encoder.device_featurize = True
         logger.info("device featurizer on")
+    # gfkb.int8_mirror, likewise: true builds the mirror of the rows the
+    # engine holds and keeps it on across store swaps; false touches nothing
+    if bool(config.get("gfkb.int8_mirror", False)):
+        from kakveda_amd.gfkb.engine import EmbeddingStore
+
+        if not isinstance(engine.store, EmbeddingStore):
+            raise NotImplementedError(
+                f"gfkb.int8_mirror is not supported on {type(engine.store).__name__}"
+            )
+        engine.int8_mirror = True
+        engine.store.enable_mirror()
+        logger.info("int8 mirror on")
 
 
 def create_app(
@@ -188,7 +200,8 @@ def create_app(
 ) -> FastAPI:
     """``config`` is a ``ConfigStore`` (or anything with its ``get``); its
     ``gfkb.routed`` block opts the service into routed search, its
-    ``gfkb.device_featurize`` flag into hashing texts on the device."""
+    ``gfkb.device_featurize`` flag into hashing texts on the device, its
+    ``gfkb.int8_mirror`` flag into the int8 row mirror."""
     app = FastAPI(title="Kakveda-AMD GFKB")
     if engine is None:
         import torch
