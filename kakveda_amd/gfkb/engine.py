@@ -79,7 +79,10 @@ class EmbeddingStore:
     row, created, grown, split and adopted with the rows as the labels are.
     Exact searches of up to ``ops.Q8_MAX_B`` queries scan it instead of the
     bf16 rows and rescore the survivors from them (``ops.cosine_topk_q8``):
-    the same answer from about half the bytes. The routed scans stay bf16.
+    the same answer from about half the bytes. Unfiltered batches of at least
+    ``ops.Q8_BATCH_MIN_B`` queries are screened with it on the int8 matrix
+    cores and rescored the same way: the same answer from about half the
+    matrix-core cycles. The routed scans stay bf16.
 
     Optional routed search: ``build_index()`` attaches an ``IvfIndex``
     (gfkb/ivf.py) and ``search(..., nprobe=n)`` then scans only the n best
@@ -125,6 +128,9 @@ class EmbeddingStore:
         self.int8_mirror = False
         self._codes: List[torch.Tensor] = []
         self._meta: List[torch.Tensor] = []
+        #: per segment, at least the largest norm of its mirrored rows (fp32
+        #: [1]; q8_plan.h cnorm), raised where the rows are quantised
+        self._cnorm: List[torch.Tensor] = []
         if int8_mirror:
             self.enable_mirror()
 
@@ -139,7 +145,9 @@ class EmbeddingStore:
         seg = self._segments[seg_no]
         for a in range(lo, hi, MIRROR_CHUNK_ROWS):
             b = min(a + MIRROR_CHUNK_ROWS, hi)
-            ops.quantize_rows_q8(seg[a:b], self._codes[seg_no], self._meta[seg_no], a)
+            ops.quantize_rows_q8(
+                seg[a:b], self._codes[seg_no], self._meta[seg_no], a, self._cnorm[seg_no]
+            )
 
     def enable_mirror(self) -> None:
         """Turn the int8 mirror on: allocate it beside every segment and
@@ -151,6 +159,7 @@ class EmbeddingStore:
         pairs = [self._new_mirror(int(seg.shape[0])) for seg in self._segments]
         self._codes = [c for c, _m in pairs]
         self._meta = [m for _c, m in pairs]
+        self._cnorm = [ops.new_q8_cnorm(self.device) for _ in pairs]
         for i, (_seg, valid, _base) in enumerate(self._live_segments()):
             self._quantize(i, 0, valid)
         self.int8_mirror = True
@@ -226,6 +235,7 @@ class EmbeddingStore:
                     codes, meta = self._new_mirror(self.segment_rows)
                     self._codes.append(codes)
                     self._meta.append(meta)
+                    self._cnorm.append(ops.new_q8_cnorm(self.device))
 
     def adopt(self, data: torch.Tensor, labels: Optional[torch.Tensor] = None) -> None:
         """Take ownership of a pre-built [n, D] row tensor (zero copy) —
@@ -248,6 +258,7 @@ class EmbeddingStore:
         if self.int8_mirror:
             codes, meta = self._new_mirror(n)
             self._codes, self._meta = [codes], [meta]
+            self._cnorm = [ops.new_q8_cnorm(self.device)]
             self._quantize(0, 0, n)
 
     def append(self, rows: torch.Tensor, labels: Optional[torch.Tensor] = None) -> int:
@@ -479,8 +490,13 @@ class EmbeddingStore:
         segs = self._live_segments(count)
         w = None if want is None else want.to(device=self.device, dtype=torch.int32)
 
-        # exact from here on; small batches read the int8 mirror when it is on
-        q8 = self.int8_mirror and q.shape[0] <= ops.Q8_MAX_B
+        # exact from here on. With the int8 mirror on, small batches scan it
+        # (ops.Q8_MAX_B) and unfiltered batches from ops.Q8_BATCH_MIN_B
+        # queries on are screened with it; both rescore from the bf16 rows.
+        q8 = self.int8_mirror and (
+            q.shape[0] <= ops.Q8_MAX_B
+            or (want is None and q.shape[0] >= ops.Q8_BATCH_MIN_B)
+        )
 
         def topk(seg_no: int, n: int):
             seg, labels = self._segments[seg_no], self._labels[seg_no]
@@ -488,6 +504,7 @@ class EmbeddingStore:
                 return ops.cosine_topk_q8(
                     q, seg, self._codes[seg_no], self._meta[seg_no], k, valid_n=n,
                     labels=None if w is None else labels, want=w,
+                    cnorm=self._cnorm[seg_no],
                 )
             if w is None:
                 return ops.cosine_topk(q, seg, k, valid_n=n)

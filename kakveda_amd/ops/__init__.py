@@ -252,6 +252,33 @@ _Q8_CAP = 32768
 #: 1.02-1.03x (spread <= 0.7%) at B=1, 2, 4, and 0.99-1.00x at B=8: a loss.
 Q8_MAX_B = 4
 
+#: largest D of the batched int8 screen (q8_plan.h Q8_SCREEN_MAX_D: the int32
+#: dot of the codes must convert to fp32 exactly)
+Q8_SCREEN_MAX_D = 1024
+
+#: Smallest batch at which ``EmbeddingStore.search`` and ``cosine_topk_q8``
+#: screen the 8-phase emission scan with int8 (``q8_batch_in_plan``): the
+#: smallest B of the sweep (profiles/q8_batch_screen.md: D=768, k=5, isotropic
+#: rows and queries, both arms alternating in one process, 8 timings each). At
+#: 10M rows the int8 arm wins at every B measured: 1.41x at B=16 and 32, 1.33x
+#: at 64, 1.30x at 128, 1.24x at 256, 1.26x at 512, 1.30x at 1024, 1.32x at
+#: 2048, with both arms' spread under 3.5% (one 11% outlier at B=16). Batches
+#: of 9..15 queries were not measured; they pay the same single 256-row tile.
+Q8_BATCH_MIN_B = 16
+
+#: Fewest rows (of one store segment) at which they do so. The same sweep at
+#: 1.25M rows: 1.03-1.07x up to B=1024, inside the bf16 arm's spread (up to
+#: 6.7%), and 0.95x at B=2048; bench.py (correlated queries, B=2048) loses 11%
+#: at 1.25M and 6% at 2.5M rows with the int8 arm and wins 17% at 10M (why the
+#: gain does not carry to the short launches was not profiled). So shards of
+#: that size stay on the bf16 search; the value sits just below the one size
+#: measured to win.
+Q8_BATCH_MIN_ROWS = 8_000_000
+
+#: batches of the batched screen that held a query quantised to zeros and were
+#: answered by the bf16 search (a process-wide counter)
+q8_degenerate_fallbacks = 0
+
 #: batches that overflowed the candidate buffer of the q8 path and were
 #: answered by the bf16 search instead (a process-wide counter)
 q8_overflow_fallbacks = 0
@@ -309,20 +336,49 @@ def quantize_rows_q8_ref(
     out_meta[sl] = torch.stack([scale, err32], dim=1).to(out_meta.device)
 
 
+def q8_cnorm_ref(rows: torch.Tensor) -> torch.Tensor:
+    """Reference of the ``cnorm`` of ``rows``: fp32 [1], at least the largest
+    row norm (the float64 norm, rounded up by the kernel's factor; 0 for no
+    rows)."""
+    n, D = int(rows.shape[0]), int(rows.shape[1])
+    if n == 0:
+        return torch.zeros(1, dtype=torch.float32)
+    top = rows.detach().double().cpu().norm(dim=1).max() * _q8_roundup(D) + _Q8_ERR_ABS
+    t32 = top.float()
+    if t32.double() < top:
+        t32 = torch.nextafter(t32, t32.new_tensor(float("inf")))
+    return t32.reshape(1)
+
+
+def new_q8_cnorm(device) -> torch.Tensor:
+    """A fresh ``cnorm`` scalar (fp32 [1], 0: no rows yet) for one mirror."""
+    return torch.zeros(1, dtype=torch.float32, device=device)
+
+
 def quantize_rows_q8(
-    rows: torch.Tensor, out_codes: torch.Tensor, out_meta: torch.Tensor, first_row: int = 0
+    rows: torch.Tensor,
+    out_codes: torch.Tensor,
+    out_meta: torch.Tensor,
+    first_row: int = 0,
+    cnorm: Optional[torch.Tensor] = None,
 ) -> None:
     """Quantise ``rows`` [n, D] into the int8 mirror: codes int8 go to
     ``out_codes[first_row : first_row + n]`` ([*, D]) and (scale, err) fp32
     pairs to ``out_meta[first_row : first_row + n]`` ([*, 2]), where
     ``scale * codes`` approximates the row and ``err`` is an upper bound of
-    the L2 norm of what it misses (contract: ops/hip/q8_plan.h). D must be a
-    multiple of Q8_SEG. GPU: a HIP kernel over bf16 rows; CPU: the reference."""
+    the L2 norm of what it misses (contract: ops/hip/q8_plan.h). ``cnorm``
+    (fp32 [1], ``new_q8_cnorm``) is raised to at least the largest norm of
+    these rows: the mirror's scalar the batched screen needs. D must be a
+    multiple of Q8_SEG. GPU: HIP kernels over bf16 rows; CPU: the reference."""
     _q8_check_dim(int(rows.shape[1]))
     if rows.device.type == "cuda":
-        _require_ext().quantize_rows_q8(rows.contiguous(), out_codes, out_meta, int(first_row))
+        _require_ext().quantize_rows_q8(
+            rows.contiguous(), out_codes, out_meta, int(first_row), cnorm
+        )
         return
     quantize_rows_q8_ref(rows, out_codes, out_meta, first_row)
+    if cnorm is not None:
+        torch.maximum(cnorm, q8_cnorm_ref(rows).to(cnorm.device), out=cnorm)
 
 
 def new_q8_mirror(n: int, D: int, device) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -342,13 +398,63 @@ def q8_in_plan(B: int, N: int, k: int, filtered: bool) -> bool:
     return N >= 65536 and B <= 8 and (filtered or k > 1)
 
 
-def _q8_sample_rows(N: int, filtered: bool) -> int:
-    """Rows the emission prepass of a B <= 8 request samples under the
-    default plan (knn_plan.h: preg sampled chunks of PRE_TILES 128-column
-    tiles), for the reference's floors."""
+def _q8_batch_env() -> bool:
+    """KAKVEDA_Q8_BATCH as the extension reads it (knn_plan.h parse_knn_env):
+    unset or 1 is on, 0 forces the bf16 path, anything else is refused."""
+    v = os.environ.get("KAKVEDA_Q8_BATCH", "")
+    if v in ("", "1"):
+        return True
+    if v == "0":
+        return False
+    raise ValueError(
+        f"KAKVEDA_Q8_BATCH='{v}' is not a setting; accepted: 1 (default: "
+        "cosine_topk_q8 screens batches with int8), 0 (it answers them with "
+        "the bf16 search)"
+    )
+
+
+def q8_batch_in_plan(
+    B: int,
+    N: int,
+    k: int,
+    D: int,
+    filtered: bool,
+    min_b: Optional[int] = None,
+    min_rows: Optional[int] = None,
+) -> bool:
+    """Whether ``cosine_topk_q8`` screens this request with int8 in the place
+    of the 8-phase bf16 emission scan: unfiltered, N >= 65,536, k > 1, more
+    queries than the streaming kernel takes and at least ``min_b`` (default
+    ``Q8_BATCH_MIN_B``), at least ``min_rows`` rows (default
+    ``Q8_BATCH_MIN_ROWS``), D a multiple of Q8_SEG up to Q8_SCREEN_MAX_D, and
+    KAKVEDA_Q8_BATCH not 0. The two defaults are speed thresholds: the path is
+    exact wherever the other conditions hold."""
+    floor_b = Q8_BATCH_MIN_B if min_b is None else int(min_b)
+    floor_n = Q8_BATCH_MIN_ROWS if min_rows is None else int(min_rows)
+    return (
+        not filtered
+        and N >= 65536
+        and N >= floor_n
+        and k > 1
+        and B > 8
+        and floor_b > 0
+        and B >= floor_b
+        and D >= Q8_SEG
+        and D % Q8_SEG == 0
+        and D <= Q8_SCREEN_MAX_D
+        and _q8_batch_env()
+    )
+
+
+def _q8_sample_rows(N: int, filtered: bool, B: int = 1) -> int:
+    """Rows the emission prepass of a request samples under the default plan
+    (knn_plan.h: preg sampled chunks of PRE_TILES 128-column tiles), for the
+    reference's floors. ``B`` matters above 8 queries, where the chunking is
+    the 8-phase kernel's over ceil(B / 256) row tiles."""
     tile, target = (128, 2048) if filtered else (256, 512)
     ntiles = -(-N // tile)
-    chunk_tiles = max(4, min(-(-ntiles // target), 128))
+    row_tiles = -(-B // tile)
+    chunk_tiles = max(4, min(-(-ntiles * row_tiles // target), 128))
     nchunks = (-(-ntiles // chunk_tiles) + 7) & ~7
     preg = min(256, nchunks) & ~7
     return min(N, preg * 8 * 128)
@@ -397,6 +503,98 @@ def q8_emit_mask_ref(
     return elig & (s8 + slack >= floor[:, None])
 
 
+def q8_screen_params_ref(
+    queries: torch.Tensor, floors: torch.Tensor, cnorm: torch.Tensor
+) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, int]:
+    """The per-call side of the batched screen (q8_plan.h "Screening test"),
+    in torch: the queries quantised by the corpus quantiser, ``T`` fp32 [B]
+    (``q8_screen_threshold`` of each row's ``floors`` entry, evaluated in fp32
+    step by step), ``kappa`` fp32 [1] (the largest ``q8_screen_kappa``) and
+    the number of degenerate queries (scale 0: their T is +1e38). Returns
+    (qcodes int8 [B, D] on the CPU, T, kappa, degenerate)."""
+    B, D = int(queries.shape[0]), int(queries.shape[1])
+    qcodes = torch.zeros(B, D, dtype=torch.int8)
+    qmeta = torch.zeros(B, 2, dtype=torch.float32)
+    quantize_rows_q8_ref(queries, qcodes, qmeta)
+    sq, errq = qmeta[:, 0], qmeta[:, 1]
+    live = sq > 0
+    safe = torch.where(live, sq, torch.ones_like(sq))
+    f32 = lambda x: torch.tensor(x, dtype=torch.float32)  # noqa: E731
+    up = f32(_q8_roundup(D))
+    sumsq = (qcodes.long() ** 2).sum(dim=1).float()
+    nqh = safe * torch.sqrt(sumsq) * up + f32(_Q8_ERR_ABS)
+    kap = (nqh / safe) * f32(1.0 + 2.0 ** -22)
+    kappa = torch.where(live, kap, torch.zeros_like(kap)).max().reshape(1)
+    slack = f32(D * 2.0 ** -22)
+    fl = floors.detach().float().cpu()
+    e = errq * cnorm.detach().float().cpu().reshape(()) * f32(1.0 + 2.0 ** -22)
+    mag = fl.abs() + e + slack
+    num = fl - e - slack - mag * f32(2.0 ** -21)
+    t = num / safe
+    t = t - t.abs() * f32(2.0 ** -22)
+    T = torch.where(live, t, torch.full_like(t, 1e38))
+    return qcodes, T, kappa, int((~live).sum())
+
+
+def q8_screen_mask_ref(
+    qcodes: torch.Tensor,
+    codes: torch.Tensor,
+    meta: torch.Tensor,
+    T: torch.Tensor,
+    kappa: torch.Tensor,
+    valid_n: int,
+    band: bool = False,
+):
+    """The batched screen's candidate mask in torch: bool [B, valid_n], true
+    where ``v = acc * scale_c + kappa * err_c >= T_r`` with ``acc`` the exact
+    dot of the codes (q8_plan.h q8_screen_fast; the kernel rounds v once, here
+    it is formed in float64 from the fp32 product ``kappa * err_c``). With
+    ``band`` also the pairs whose v lies within one fp32 rounding of T_r, where
+    the kernel's single rounding may decide either way."""
+    n = int(valid_n)
+    dev = codes.device
+    # products and partial sums are integers below 2^24: exact in fp32
+    acc = qcodes.to(dev).float() @ codes[:n].float().t()
+    ke = (kappa.to(dev).float().reshape(()) * meta[:n, 1]).double()
+    v = acc.double() * meta[:n, 0].double()[None, :] + ke[None, :]
+    Td = T.to(dev).double()[:, None]
+    mask = v >= Td
+    if not band:
+        return mask
+    near = (v - Td).abs() <= torch.maximum(v.abs(), Td.abs()) * 2.0 ** -23
+    return mask, near
+
+
+def _q8_batch_ref(queries, corpus, codes, meta, cnorm, k, n):
+    """The batched path of ``cosine_topk_q8_ref``: (scores, idx), or None when
+    the batch falls back (and which counter it bumped)."""
+    global q8_overflow_fallbacks, q8_degenerate_fallbacks
+    B = queries.shape[0]
+    q = queries.float()
+    ns = _q8_sample_rows(n, False, B)
+    samp = q @ corpus[:ns].float().t()
+    seeds = torch.topk(samp, min(KMAX, ns), dim=1)
+    floors = seeds.values[:, -1] if ns >= KMAX else samp.new_full((B,), -1e30)
+    if cnorm is None:
+        cnorm = q8_cnorm_ref(corpus[:n])
+    qcodes, T, kappa, degenerate = q8_screen_params_ref(queries, floors, cnorm)
+    if degenerate:
+        q8_degenerate_fallbacks += 1
+        return None
+    mask = q8_screen_mask_ref(qcodes, codes, meta, T, kappa, n).to(q.device)
+    if ns < n:
+        # the main launch starts after the sample; its top-KMAX are seeded
+        mask[:, :ns] = False
+        mask[:, :ns].scatter_(1, seeds.indices, True)
+    if int(mask.sum(dim=1).max()) > _Q8_CAP:
+        q8_overflow_fallbacks += 1
+        return None
+    sims = (q @ corpus[:n].float().t()).masked_fill(~mask, float("-inf"))
+    scores, idx = torch.topk(sims, min(k, n), dim=1)
+    idx = torch.where(torch.isinf(scores) & (scores < 0), torch.full_like(idx, -1), idx)
+    return _pad_topk(scores.float(), idx.long(), k)
+
+
 def cosine_topk_q8_ref(
     queries: torch.Tensor,
     corpus: torch.Tensor,
@@ -406,14 +604,20 @@ def cosine_topk_q8_ref(
     valid_n: Optional[int] = None,
     labels: Optional[torch.Tensor] = None,
     want: Optional[torch.Tensor] = None,
+    cnorm: Optional[torch.Tensor] = None,
+    batch_min_b: Optional[int] = None,
+    batch_min_rows: Optional[int] = None,
 ) -> Tuple[torch.Tensor, torch.Tensor]:
     """``cosine_topk_q8`` in torch (fp32 accumulate): floors from the sampled
     rows, emission from the int8 mirror with each row's error margin
     (``q8_emit_mask_ref``), exact scores of the emitted rows from ``corpus``,
     top-k of those. A query with more than the candidate buffer's capacity
     of emitted rows sends the batch to the plain reference search and bumps
-    ``q8_overflow_fallbacks``, as on the GPU. Requests outside
-    ``q8_in_plan`` run the plain reference search."""
+    ``q8_overflow_fallbacks``, as on the GPU. A request of the batched screen
+    (``q8_batch_in_plan``) takes that path's reference: floors and seeds from
+    the sample, ``q8_screen_mask_ref`` over the rest, exact scores of the
+    survivors. Other requests outside ``q8_in_plan`` run the plain reference
+    search."""
     global q8_overflow_fallbacks
     n = int(valid_n) if valid_n is not None else corpus.shape[0]
     B = queries.shape[0]
@@ -425,6 +629,12 @@ def cosine_topk_q8_ref(
             return cosine_topk_filtered_ref(queries, corpus, labels, want, k, n)
         return cosine_topk_ref(queries, corpus, k, n)
 
+    if n > 0 and q8_batch_in_plan(
+        B, n, min(int(k), KMAX), int(queries.shape[1]), filtered, batch_min_b,
+        batch_min_rows,
+    ):
+        got = _q8_batch_ref(queries, corpus, codes, meta, cnorm, k, n)
+        return plain() if got is None else got
     if n <= 0 or not q8_in_plan(B, n, min(int(k), KMAX), filtered):
         return plain()
     mask = q8_emit_mask_ref(queries, corpus, codes, meta, n, labels, want)
@@ -438,6 +648,58 @@ def cosine_topk_q8_ref(
     return _pad_topk(scores.float(), idx.long(), k)
 
 
+def q8_cnorm(rows: torch.Tensor) -> torch.Tensor:
+    """``cnorm`` of ``rows`` (fp32 [1] on their device): at least their largest
+    L2 norm. One pass over the rows; a store keeps it beside its mirror."""
+    if rows.device.type != "cuda":
+        return q8_cnorm_ref(rows)
+    D = int(rows.shape[1])
+    _q8_check_dim(D)
+    out = new_q8_cnorm(rows.device)
+    # the quantiser's companion kernel, without keeping the codes
+    codes, meta = new_q8_mirror(min(int(rows.shape[0]), 1 << 16), D, rows.device)
+    for a in range(0, int(rows.shape[0]), 1 << 16):
+        b = min(a + (1 << 16), int(rows.shape[0]))
+        _require_ext().quantize_rows_q8(rows[a:b].contiguous(), codes, meta, 0, out)
+    return out
+
+
+def q8_screen_probe(
+    queries: torch.Tensor,
+    corpus: torch.Tensor,
+    codes: torch.Tensor,
+    meta: torch.Tensor,
+    cnorm: torch.Tensor,
+    k: int,
+    valid_n: Optional[int] = None,
+    cap: Optional[int] = None,
+):
+    """The batched screen up to the merge, on the GPU: a dict with ``counts``
+    and ``first`` (i32 [B]: entries per row, and how many of them are seeds),
+    ``before`` and ``after`` (i64 [B, cap]: the candidate lists ahead of and
+    behind the rescore, packed ``enc(score) << 32 | 0x7fffffff - column``),
+    ``T`` (fp32 [B]), ``kappa`` (fp32 [1]) and ``floors`` (fp32 [B], the
+    prepass floors)."""
+    n = int(valid_n) if valid_n is not None else corpus.shape[0]
+    counts, first, before, after, T, kappa, rowthr = _require_ext().q8_screen_probe(
+        queries, corpus, codes, meta, cnorm, min(int(k), KMAX), n, int(cap or 0)
+    )
+    return dict(counts=counts, first=first, before=before, after=after, T=T,
+                kappa=kappa, floors=_dec_f32(rowthr.long() & 0xFFFFFFFF))
+
+
+def _dec_f32(u: torch.Tensor) -> torch.Tensor:
+    """kernels_impl.h dec_f32 on order-encoded words held in int64."""
+    bits = torch.where(u >= 2 ** 31, u ^ 0x80000000, ~u & 0xFFFFFFFF)
+    bits = bits - ((bits >= 2 ** 31).long() << 32)  # as signed 32-bit
+    return bits.to(torch.int32).view(torch.float32)
+
+
+def q8_unpack(entries: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(scores fp32, columns i64) of packed candidate entries (i64)."""
+    return _dec_f32((entries >> 32) & 0xFFFFFFFF), 0x7FFFFFFF - (entries & 0xFFFFFFFF)
+
+
 def cosine_topk_q8(
     queries: torch.Tensor,
     corpus: torch.Tensor,
@@ -447,6 +709,10 @@ def cosine_topk_q8(
     valid_n: Optional[int] = None,
     labels: Optional[torch.Tensor] = None,
     want: Optional[torch.Tensor] = None,
+    cnorm: Optional[torch.Tensor] = None,
+    batch_min_b: Optional[int] = None,
+    cap: Optional[int] = None,
+    batch_min_rows: Optional[int] = None,
 ) -> Tuple[torch.Tensor, torch.Tensor]:
     """``cosine_topk`` (``cosine_topk_filtered`` when ``labels``/``want`` are
     given) that reads the int8 mirror of the corpus where the request is one
@@ -459,8 +725,21 @@ def cosine_topk_q8(
     other request runs the bf16 search unchanged, and so does a batch whose
     candidates overflow their buffer (``q8_overflow_fallbacks`` counts them).
     Shapes, padding and the KMAX clamp as ``cosine_topk``/``_filtered``; D
-    must be a multiple of Q8_SEG."""
-    global q8_overflow_fallbacks
+    must be a multiple of Q8_SEG.
+
+    Batches (``q8_batch_in_plan``: the unfiltered 8-phase emission request
+    with at least ``batch_min_b`` queries and ``batch_min_rows`` rows, default
+    ``Q8_BATCH_MIN_B`` and ``Q8_BATCH_MIN_ROWS``) are
+    screened instead: the emission kernel runs on int8 codes of queries and
+    rows with ``v_mfma_i32_16x16x64_i8``, every (query, row) whose int8 score
+    plus the known errors of both sides could reach the prepass floor is
+    rescored with the bf16 kernel's own MFMA chain, and the unchanged merge
+    follows: scores and ids are bit-equal to ``cosine_topk``'s. ``cnorm`` is
+    the mirror's largest row norm (``quantize_rows_q8``); None computes it
+    from ``corpus`` on every call. ``cap`` overrides the per-query candidate
+    capacity of that path (tests). A batch holding a query that quantises to
+    zeros is answered by the bf16 search (``q8_degenerate_fallbacks``)."""
+    global q8_overflow_fallbacks, q8_degenerate_fallbacks
     _q8_check_dim(int(queries.shape[1]))
     if (labels is None) != (want is None):
         raise ValueError("labels and want go together")
@@ -472,7 +751,10 @@ def cosine_topk_q8(
             torch.full((B, k), -1, dtype=torch.int64, device=queries.device),
         )
     if queries.device.type != "cuda":
-        return cosine_topk_q8_ref(queries, corpus, codes, meta, k, n, labels, want)
+        return cosine_topk_q8_ref(
+            queries, corpus, codes, meta, k, n, labels, want, cnorm, batch_min_b,
+            batch_min_rows,
+        )
     ext = _require_ext()
     kk = min(int(k), KMAX)
     filt = {}
@@ -481,10 +763,18 @@ def cosine_topk_q8(
             labels=labels.to(device=corpus.device, dtype=torch.int32).contiguous(),
             want=want.to(device=queries.device, dtype=torch.int32).contiguous(),
         )
-    scores, idx, overflowed, _counts = ext.cosine_topk_q8(
+    min_b = Q8_BATCH_MIN_B if batch_min_b is None else int(batch_min_b)
+    if q8_batch_in_plan(
+        B, n, kk, int(queries.shape[1]), want is not None, min_b, batch_min_rows
+    ):
+        if cnorm is None:
+            cnorm = q8_cnorm(corpus[:n])
+        filt.update(cnorm=cnorm, batch_min_b=min_b, cap=int(cap or 0))
+    scores, idx, fallback, _counts = ext.cosine_topk_q8(
         queries, corpus, codes, meta, kk, n, **filt
     )
-    q8_overflow_fallbacks += int(overflowed)
+    q8_overflow_fallbacks += int(fallback == 1)
+    q8_degenerate_fallbacks += int(fallback == 2)
     if want is not None:
         scores = torch.where(idx < 0, torch.full_like(scores, float("-inf")), scores)
     return _pad_topk(scores, idx, k)

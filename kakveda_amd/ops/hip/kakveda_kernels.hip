@@ -11,6 +11,7 @@
 #include "ivf_batch_impl.h"
 #include "featurize_impl.h"
 #include "q8_impl.h"
+#include "q8_screen_impl.h"
 
 using namespace kakveda;
 
@@ -422,6 +423,13 @@ void check_q8_mirror(const torch::Tensor& codes, const torch::Tensor& meta,
               "meta must be contiguous fp32 [>= ", rows, ", 2] on the rows' device");
 }
 
+void check_q8_cnorm(const torch::Tensor& cnorm, const torch::Device& dev) {
+  TORCH_CHECK(cnorm.is_cuda() && cnorm.device() == dev &&
+                  cnorm.scalar_type() == torch::kFloat32 && cnorm.numel() == 1 &&
+                  cnorm.is_contiguous(),
+              "cnorm must be one fp32 value on the rows' device");
+}
+
 // Stage 1 of the q8 search into e.cand / e.ccount.
 void launch_q8_emit(const KnnArgs& a, const KnnPlan& p, const torch::Tensor& codes,
                     const torch::Tensor& meta, const Floors& f, EmitBufs& e,
@@ -481,11 +489,13 @@ Q8Checked check_q8_search(const torch::Tensor& queries, const torch::Tensor& cor
 }  // namespace
 
 void quantize_rows_q8(torch::Tensor rows, torch::Tensor out_codes,
-                      torch::Tensor out_meta, int64_t first_row) {
+                      torch::Tensor out_meta, int64_t first_row,
+                      c10::optional<torch::Tensor> cnorm) {
   check_bf16_2d(rows, "rows");
   const int64_t n = rows.size(0), D = rows.size(1);
   TORCH_CHECK(first_row >= 0, "first_row must be >= 0");
   check_q8_mirror(out_codes, out_meta, rows.device(), first_row + n, D);
+  if (cnorm) check_q8_cnorm(*cnorm, rows.device());
   if (n == 0) return;
   const int blocks = (int)std::min((n + 31) / 32, (int64_t)8192);
   hipLaunchKernelGGL(q8_quantize_kernel, dim3(blocks), dim3(256), 0,
@@ -493,26 +503,152 @@ void quantize_rows_q8(torch::Tensor rows, torch::Tensor out_codes,
                      (const bf16_t*)rows.data_ptr(), (long)n, (int)D,
                      (signed char*)out_codes.data_ptr<int8_t>(),
                      out_meta.data_ptr<float>(), (long)first_row);
+  // the segment's cnorm (q8_plan.h): raised to the largest norm of these rows
+  if (cnorm)
+    hipLaunchKernelGGL(q8_cnorm_kernel, dim3(blocks), dim3(256), 0,
+                       c10::hip::getCurrentHIPStream().stream(),
+                       (const bf16_t*)rows.data_ptr(), (long)n, (int)D,
+                       cnorm->data_ptr<float>());
   C10_HIP_KERNEL_LAUNCH_CHECK();
 }
+
+namespace {
+
+// The batched int8 screen (q8_screen_impl.h) up to and including the rescore:
+// quantise the queries, the unchanged floors and seeds, T_r and kappa, the
+// screen over the codes, emit_bin, then the bf16 scores of every emitted
+// entry. Afterwards e.cand / e.ccount hold what the bf16 emission launch
+// leaves there plus the screen's false positives, all with bf16 scores.
+struct Q8Screen {
+  EmitBufs e;
+  torch::Tensor first;      // i32 [B]: entries seeded before the screen
+  torch::Tensor thrT;       // f32 [B]: T_r
+  torch::Tensor small;      // i32 [2]: bits of kappa, degenerate rows
+  torch::Tensor rowthr;     // u32 [B]: the prepass floors, order-encoded
+  torch::Tensor before;     // the candidate buffer ahead of the rescore (probe)
+  long cap, seg;
+};
+
+Q8Screen run_q8_screen(const KnnArgs& a, const KnnPlan& p, const KnnEnv& env,
+                       const torch::Tensor& codes, const torch::Tensor& meta,
+                       const torch::Tensor& cnorm, long cap_override,
+                       bool keep_before) {
+  const auto i8 = torch::TensorOptions().dtype(torch::kInt8).device(a.dev);
+  auto qcodes = torch::empty({(long)a.B, (long)a.D}, i8);
+  auto qmeta = torch::empty({(long)a.B, 2L}, a.f32());
+  hipLaunchKernelGGL(q8_quantize_kernel, dim3((a.B + 31) / 32), dim3(256), 0,
+                     a.stream, a.q, (long)a.B, a.D,
+                     (signed char*)qcodes.data_ptr<int8_t>(),
+                     qmeta.data_ptr<float>(), 0L);
+  const Floors f = run_emission_floors(a, p.pre_grid, p.pre_tiles,
+                                       p.prepass_mode, KMAX);
+  Q8Screen s;
+  s.rowthr = f.rowthr;
+  s.cap = cap_override > 0 ? cap_override : p.cap;
+  s.seg = emit_seg_cap(a.B, s.cap, p.mch, env.seg);
+  s.thrT = torch::empty({(long)a.B}, a.f32());
+  s.small = torch::zeros({2L}, a.i32());
+  hipLaunchKernelGGL(q8_screen_prep, dim3((a.B + 3) / 4), dim3(256), 0, a.stream,
+                     (const signed char*)qcodes.data_ptr<int8_t>(),
+                     (const float*)qmeta.data_ptr<float>(),
+                     (const unsigned*)f.rowthr.data_ptr<int>(),
+                     (const float*)cnorm.data_ptr<float>(), a.B, a.D,
+                     s.thrT.data_ptr<float>(), (float*)s.small.data_ptr<int>(),
+                     s.small.data_ptr<int>() + 1);
+  const bool seeded = p.skip_tiles > 0;
+  s.e = new_emit_bufs(a, s.cap, p.mch, s.seg, seeded ? &f : nullptr);
+  s.first = s.e.ccount.clone();
+  unsigned long long* const eseg = (unsigned long long*)s.e.eseg.data_ptr<int64_t>();
+  unsigned* const esegcnt = (unsigned*)s.e.esegcnt.data_ptr<int>();
+  unsigned long long* const cand = (unsigned long long*)s.e.cand.data_ptr<int64_t>();
+  unsigned* const ccount = (unsigned*)s.e.ccount.data_ptr<int>();
+  const dim3 grid(p.mch.nchunks, p.mch.row_tiles);
+  hipLaunchKernelGGL(cosine_topk_screen8p_i8, grid, dim3(THREADS8), 0, a.stream,
+                     (const signed char*)qcodes.data_ptr<int8_t>(),
+                     (const signed char*)codes.data_ptr<int8_t>(),
+                     (const float*)meta.data_ptr<float>(),
+                     (const float*)s.thrT.data_ptr<float>(),
+                     (const float*)s.small.data_ptr<int>(), a.B, a.N, a.D,
+                     p.mch.chunk_tiles, p.mch.nchunks, eseg, esegcnt, s.seg,
+                     p.skip_tiles);
+  hipLaunchKernelGGL(emit_bin, grid, dim3(256), 0, a.stream,
+                     (const unsigned long long*)eseg, (const unsigned*)esegcnt,
+                     (int)s.seg, p.mch.chunk_tiles, p.mch.nchunks, a.B, a.N, cand,
+                     ccount, s.cap, p.skip_tiles);
+  if (keep_before) s.before = s.e.cand.clone();
+  hipLaunchKernelGGL(q8_rescore_mfma, dim3(8, a.B), dim3(256), 0, a.stream, a.q,
+                     a.c, a.N, a.D, cand, (const unsigned*)ccount,
+                     (const unsigned*)s.first.data_ptr<int>(), s.cap);
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+  return s;
+}
+
+// Whether the request is the batched int8 screen's: the unfiltered 8-phase
+// emission plan, at least min_b queries, a D the screen takes, and not
+// switched off (KAKVEDA_Q8_BATCH=0; min_b <= 0: the caller does not want it).
+bool q8_screen_in_plan(const KnnArgs& a, const KnnPlan& p, const KnnEnv& env,
+                       bool filtered, int64_t min_b) {
+  return !filtered && env.q8_batch && min_b > 0 && a.B >= min_b &&
+         p.main == MainKernel::Emit8p && p.merge == MergeKernel::Emit &&
+         p.prepass && q8_screen_dim_ok(a.D) && p.mch.chunk_tiles <= 128;
+}
+
+}  // namespace
 
 // The two-stage exact search over the mirror. Where the plan of the request
 // selects the streaming small-batch kernel, stage 1 scans the int8 codes
 // (q8_emit_kernel), stage 2 rescores the candidates from the bf16 rows
-// (q8_rescore), and the existing merge and overflow check follow; every other
-// request, and an overflowed one, is answered by cosine_topk_impl as it is.
-// Returns (scores, idx, overflowed, counts): overflowed is 1 when the batch
-// fell back, counts the per-query stage-1 candidate counts (empty off-plan).
+// (q8_rescore), and the existing merge and overflow check follow. Where it
+// selects the 8-phase emission kernel and the batch has at least batch_min_b
+// queries (0: never), the int8 screen runs in that kernel's place
+// (run_q8_screen: `cnorm` is then required) with the same merge and check.
+// Every other request, and an overflowed one, is answered by cosine_topk_impl
+// as it is. Returns (scores, idx, fallback, counts): fallback is 1 when the
+// candidates overflowed (`cap` > 0 overrides their per-row capacity on the
+// batched path), 2 when a query of the batch quantised to zeros, 0 otherwise;
+// counts are the per-query stage-1 candidate counts (empty off-plan).
 std::tuple<torch::Tensor, torch::Tensor, int64_t, torch::Tensor> cosine_topk_q8(
     torch::Tensor queries, torch::Tensor corpus, torch::Tensor codes,
     torch::Tensor meta, int64_t k, int64_t valid_n,
-    c10::optional<torch::Tensor> labels, c10::optional<torch::Tensor> want) {
+    c10::optional<torch::Tensor> labels, c10::optional<torch::Tensor> want,
+    c10::optional<torch::Tensor> cnorm, int64_t batch_min_b, int64_t cap) {
   const Q8Checked c =
       check_q8_search(queries, corpus, codes, meta, k, valid_n, labels, want);
   TORCH_CHECK(queries.size(1) % BK == 0, "D must be a multiple of ", BK);
   static const KnnEnv env = parse_knn_env(std::getenv);
   const KnnArgs a = knn_args(queries, corpus, c.N);
   const KnnPlan p = plan_cosine_topk(a.B, c.N, (int)k, env, true, (bool)c.flt);
+  if (q8_screen_in_plan(a, p, env, (bool)c.flt, batch_min_b)) {
+    TORCH_CHECK(cnorm.has_value(), "cosine_topk_q8: the batched screen needs cnorm");
+    check_q8_cnorm(*cnorm, corpus.device());
+    TORCH_CHECK(plan_fits_grid(p, a.B), "cosine_topk_q8: ", a.B,
+                " query rows need more row tiles than one launch holds; split "
+                "the batch");
+    Q8Screen s = run_q8_screen(a, p, env, codes, meta, *cnorm, cap, false);
+    auto out_score = torch::empty({a.B, k}, a.f32());
+    auto out_idx = torch::empty({a.B, k}, a.i64());
+    hipLaunchKernelGGL(emit_merge_topk, dim3(a.B), dim3(256), 0, a.stream,
+                       (const unsigned long long*)s.e.cand.data_ptr<int64_t>(),
+                       (const unsigned*)s.e.ccount.data_ptr<int>(),
+                       out_score.data_ptr<float>(),
+                       (long*)out_idx.data_ptr<int64_t>(), a.B, s.cap, (int)k);
+    C10_HIP_KERNEL_LAUNCH_CHECK();
+    const long mx = (long)s.e.ccount.max().item<int>();
+    const int degen = s.small[1].item<int>();
+    if (env.emit_debug) {
+      printf("q8 screen: rows=%d max=%ld mean=%.1f cap=%ld degenerate=%d%s\n",
+             a.B, mx, s.e.ccount.to(torch::kFloat32).mean().item<float>(), s.cap,
+             degen, mx > s.cap ? "  FALLBACK" : "");
+      printf("q8 screen: segments=%ld max=%d seg=%ld skip_tiles=%d\n",
+             (long)s.e.esegcnt.size(0), s.e.esegcnt.max().item<int>(), s.seg,
+             p.skip_tiles);
+    }
+    if (degen > 0 || mx > s.cap) {
+      auto [sc, ix] = cosine_topk_impl(queries, corpus, (int)k, c.N, env, true);
+      return {sc, ix, degen > 0 ? 2 : 1, s.e.ccount};
+    }
+    return {out_score, out_idx, 0, s.e.ccount};
+  }
   if (p.main != MainKernel::SmallB || p.merge != MergeKernel::Emit) {
     auto [s, i] = cosine_topk_impl(queries, corpus, (int)k, c.N, env, true, c.flt);
     return {s, i, 0, torch::empty({0}, a.i32())};
@@ -540,6 +676,30 @@ std::tuple<torch::Tensor, torch::Tensor, int64_t, torch::Tensor> cosine_topk_q8(
     return {s, i, 1, e.ccount};
   }
   return {out_score, out_idx, 0, e.ccount};
+}
+
+// Probe of the batched screen: everything up to the merge, nothing after.
+// Returns (counts i32 [B], first i32 [B], before i64 [B, cap], after i64
+// [B, cap], T f32 [B], kappa f32 [1], the prepass floors u32 [B],
+// order-encoded): per row the entries [0, first) are the
+// seeds, [first, min(counts, cap)) the screen's candidates, packed as
+// emit_bin packs; `before` carries the screen's own score word, `after` the
+// bf16 scores. The request must be one the batched path takes at min_b = 1.
+std::vector<torch::Tensor> q8_screen_probe(
+    torch::Tensor queries, torch::Tensor corpus, torch::Tensor codes,
+    torch::Tensor meta, torch::Tensor cnorm, int64_t k, int64_t valid_n,
+    int64_t cap) {
+  const Q8Checked c = check_q8_search(queries, corpus, codes, meta, k, valid_n,
+                                      c10::nullopt, c10::nullopt);
+  check_q8_cnorm(cnorm, corpus.device());
+  static const KnnEnv env = parse_knn_env(std::getenv);
+  const KnnArgs a = knn_args(queries, corpus, c.N);
+  const KnnPlan p = plan_cosine_topk(a.B, c.N, (int)k, env, true, false);
+  TORCH_CHECK(q8_screen_in_plan(a, p, env, false, 1) && plan_fits_grid(p, a.B),
+              "q8_screen_probe: not a request of the batched int8 screen");
+  Q8Screen s = run_q8_screen(a, p, env, codes, meta, cnorm, cap, true);
+  return {s.e.ccount, s.first, s.before, s.e.cand, s.thrT,
+          s.small.slice(0, 0, 1).view(torch::kFloat32), s.rowthr};
 }
 
 // Benchmark probe: the stage-1 candidate counts of one request under both
@@ -1261,13 +1421,24 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("cosine_topk_filtered", &cosine_topk_filtered,
         "cosine top-k over the corpus rows whose label matches each query's");
   m.def("quantize_rows_q8", &quantize_rows_q8,
-        "quantise bf16 rows into the int8 mirror (codes, (scale, err))");
+        "quantise bf16 rows into the int8 mirror (codes, (scale, err))",
+        pybind11::arg("rows"), pybind11::arg("out_codes"),
+        pybind11::arg("out_meta"), pybind11::arg("first_row"),
+        pybind11::arg("cnorm") = pybind11::none());
   m.def("cosine_topk_q8", &cosine_topk_q8,
-        "exact small-batch top-k: int8 mirror scan + bf16 rescore",
+        "exact top-k over the int8 mirror: int8 scan or screen + bf16 rescore",
         pybind11::arg("queries"), pybind11::arg("corpus"), pybind11::arg("codes"),
         pybind11::arg("meta"), pybind11::arg("k"), pybind11::arg("valid_n"),
         pybind11::arg("labels") = pybind11::none(),
-        pybind11::arg("want") = pybind11::none());
+        pybind11::arg("want") = pybind11::none(),
+        pybind11::arg("cnorm") = pybind11::none(),
+        pybind11::arg("batch_min_b") = (int64_t)0,
+        pybind11::arg("cap") = (int64_t)0);
+  m.def("q8_screen_probe", &q8_screen_probe,
+        "batched int8 screen: candidate lists before and after the rescore",
+        pybind11::arg("queries"), pybind11::arg("corpus"), pybind11::arg("codes"),
+        pybind11::arg("meta"), pybind11::arg("cnorm"), pybind11::arg("k"),
+        pybind11::arg("valid_n"), pybind11::arg("cap") = (int64_t)0);
   m.def("q8_counts_probe", &q8_counts_probe,
         "stage-1 candidate counts of the int8 and the bf16 arm",
         pybind11::arg("queries"), pybind11::arg("corpus"), pybind11::arg("codes"),

@@ -40,6 +40,7 @@ struct KnnEnv {
   bool emit_debug = false;       // KAKVEDA_KNN_EMIT_DEBUG=1
   bool skip_sample = true;       // KAKVEDA_KNN_SKIP_SAMPLE: 1 (default), 0
   int pre_tiles = 0;             // KAKVEDA_KNN_PRE_TILES (0: the plan's rule)
+  bool q8_batch = true;          // KAKVEDA_Q8_BATCH: 1 (default), 0
 };
 
 // A forced size of the compact prepass's blocks, in column tiles (the
@@ -106,6 +107,14 @@ KnnEnv parse_knn_env(GetEnv&& get) {
           " is one block per sampled chunk), or unset for the plan's rule");
     e.pre_tiles = (int)t;
   }
+  v = get("KAKVEDA_Q8_BATCH");
+  const std::string qb = v ? v : "";
+  if (qb == "0") e.q8_batch = false;
+  else if (!qb.empty() && qb != "1")
+    throw std::runtime_error("KAKVEDA_Q8_BATCH='" + qb +
+                             "' is not a setting; accepted: 1 (default: "
+                             "cosine_topk_q8 screens batches with int8), 0 (it "
+                             "answers them with the bf16 search)");
   return e;
 }
 

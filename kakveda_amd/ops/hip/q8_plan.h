@@ -81,4 +81,81 @@ Q8_HD float q8_err(float norm, float amax, float scale, int D) {
 // as much again for the roundings of the test itself.
 Q8_HD float q8_slack(int D) { return (float)D * 0x1p-22f; }
 
+// ---------------------------------------------------------------------------
+// Screening test of the batched path (kernels: q8_screen_impl.h; torch
+// reference: ops/__init__.py q8_screen_mask_ref).
+//
+// The queries of a call are quantised by the corpus quantiser: q^ = sq * nq,
+// errq >= ||q - q^||, and nqh >= ||q^|| = sq * sqrt(sum nq_i^2) (the sum is an
+// exact integer below 2^24, the root and the product one rounding each:
+// q8_roundup covers them). For a corpus row c with mirror c^ = sc * nc,
+//   q.c = q^.c^ + (q - q^).c + q^.(c - c^)
+//      <= sq * sc * acc + errq * ||c|| + nqh * err_c          (Cauchy-Schwarz)
+// where acc = sum nq_i nc_i is the exact int32 dot of the codes. With cnorm >=
+// the largest row norm of the segment (kept by the store, rounded up like err),
+// (query r, column c) is a CANDIDATE iff
+//   sq_r * sc_c * acc + nqh_r * err_c + errq_r * cnorm + q8_slack(D) >= floor_r
+// (q8_screen_ref below). floor_r is the floor the bf16 prepass published; the
+// bf16 kernels emit a pair iff their fp32 score reaches it, and that score is
+// within D * 2^-24 of q.c for unit rows, the first half of q8_slack. So every
+// pair the bf16 search emits is a candidate.
+//
+// The kernel's form (q8_screen_fast): with kappa >= nqh_r / sq_r for every row
+// of the launch and sq_r > 0,
+//   v = fma(float(acc), sc_c, kappa * err_c)   >=   T_r
+//   T_r <= (floor_r - errq_r * cnorm - q8_slack(D)) / sq_r
+// holds for every candidate: dividing the test by sq_r and replacing
+// nqh_r / sq_r by the larger kappa only grows the left side. float(acc) is
+// exact for |acc| <= D * 127^2 < 2^24, i.e. D <= Q8_SCREEN_MAX_D. The roundings
+// of v (two) and of T_r (q8_screen_threshold lowers it explicitly past its
+// own) are relative 2^-24 of magnitudes that, times sq_r, stay below 2 for
+// unit rows: under 2^-21 in score units against the D * 2^-23 >= 2^-16 the
+// second half of q8_slack leaves for them. A query with sq_r == 0 (stored as
+// zeros) has no T_r: a batch that holds one takes the bf16 path.
+// ---------------------------------------------------------------------------
+constexpr int Q8_SCREEN_MAX_D = 1024;  // 1024 * 127^2 < 2^24 <= 1152 * 127^2
+
+Q8_HD bool q8_screen_dim_ok(long D) { return q8_dim_ok(D) && D <= Q8_SCREEN_MAX_D; }
+
+// nqh >= ||sq * nq|| from the exact integer sum of the squared codes.
+Q8_HD float q8_code_norm(float sq, long sumsq, int D) {
+  return sq * sqrtf((float)sumsq) * q8_roundup(D) + Q8_ERR_ABS;
+}
+
+// Norm of a row from the fp32 sum of its squares, rounded up (cnorm's terms).
+Q8_HD float q8_norm_up(float sumsq, int D) {
+  return sqrtf(sumsq) * q8_roundup(D) + Q8_ERR_ABS;
+}
+
+// kappa's term of one row: >= nqh / sq (sq > 0).
+Q8_HD float q8_screen_kappa(float nqh, float sq) {
+  return (nqh / sq) * (1.0f + 0x1p-22f);
+}
+
+// T_r, rounded down past the three roundings of its evaluation (sq > 0).
+// NEG_INF-like floors (nothing published) give a hugely negative or -inf T:
+// every column is then a candidate, as under the bf16 kernels.
+Q8_HD float q8_screen_threshold(float floor, float sq, float errq, float cnorm,
+                                int D) {
+  const float e = errq * cnorm * (1.0f + 0x1p-22f);
+  const float mag = fabsf(floor) + e + q8_slack(D);
+  const float num = floor - e - q8_slack(D) - mag * 0x1p-21f;
+  const float t = num / sq;
+  return t - fabsf(t) * 0x1p-22f;
+}
+
+// The contract, serially and in double: is (query, column) a candidate?
+inline bool q8_screen_ref(long acc, float sq, float sc, float nqh, float err,
+                          float errq, float cnorm, float floor, int D) {
+  const double lhs = (double)sq * (double)sc * (double)acc +
+                     (double)nqh * (double)err + (double)errq * (double)cnorm +
+                     (double)q8_slack(D);
+  return lhs >= (double)floor;
+}
+
+// The kernel's test, as the kernel evaluates it.
+Q8_HD bool q8_screen_fast(int acc, float sc, float err, float kappa, float T) {
+  return fmaf((float)acc, sc, kappa * err) >= T;
+}
+
 }  // namespace kakveda

@@ -29,12 +29,34 @@ class ShardedStore:
     every shard.
     """
 
-    def __init__(self, dim: int, device: str = "cpu", capacity: int = 1024):
+    def __init__(
+        self,
+        dim: int,
+        device: str = "cpu",
+        capacity: int = 1024,
+        int8_mirror: Optional[bool] = None,
+    ):
         import os
+
+        from kakveda_amd import ops
 
         self.rank, self.world = get_world()
         self.dim = dim
-        self.local = EmbeddingStore(dim, device=device, capacity=capacity)
+        # The bulk store keeps the int8 mirror of its shard by default where
+        # the batched screen can use it (ops.cosine_topk_q8): on a HIP device
+        # with a D the mirror takes. load_shard and append quantise the rows
+        # once, at ingest; the mirror adds (D + 8) / (2 D) of the shard's
+        # memory (50.5% at D = 768). None: that default; CPU stores stay off.
+        if int8_mirror is None:
+            int8_mirror = (
+                torch.device(device).type == "cuda"
+                and dim >= ops.Q8_SEG
+                and dim % ops.Q8_SEG == 0
+            )
+        self.int8_mirror = bool(int8_mirror)
+        self.local = EmbeddingStore(
+            dim, device=device, capacity=capacity, int8_mirror=self.int8_mirror
+        )
         self.total = 0  # global row count
         # test hook: run the all-gather merge even at world=1 so a 1-GPU
         # box executes the real RCCL collective path (RCCL refuses two
