@@ -266,14 +266,17 @@ Q8_SCREEN_MAX_D = 1024
 #: of 9..15 queries were not measured; they pay the same single 256-row tile.
 Q8_BATCH_MIN_B = 16
 
-#: Fewest rows (of one store segment) at which they do so. The same sweep at
-#: 1.25M rows: 1.03-1.07x up to B=1024, inside the bf16 arm's spread (up to
-#: 6.7%), and 0.95x at B=2048; bench.py (correlated queries, B=2048) loses 11%
-#: at 1.25M and 6% at 2.5M rows with the int8 arm and wins 17% at 10M (why the
-#: gain does not carry to the short launches was not profiled). So shards of
-#: that size stay on the bf16 search; the value sits just below the one size
-#: measured to win.
-Q8_BATCH_MIN_ROWS = 8_000_000
+#: Fewest rows (of one store segment) at which they do so. With the screen's
+#: floors raised between stages (profiles/q8_staged_floors.md) bench.py
+#: (correlated queries, B=2048, three alternating runs per arm) runs 7.03-7.12
+#: ms/step with the int8 arm against 9.36-9.58 on bf16 at 2.5M rows, and
+#: 4.60-4.63 against 5.02-5.14 at 1.25M: 1.32x and 1.10x, beyond both arms'
+#: spread. Before the stages the int8 arm lost 6% and 11% there and the gate
+#: stood at 8M rows. The earlier sweep at 1.25M rows (one stage, isotropic
+#: queries) had the int8 arm at 1.03-1.07x up to B=1024, inside the bf16 arm's
+#: spread: not a loss. Smaller shards were not measured; the value sits just
+#: below the smallest size measured to win.
+Q8_BATCH_MIN_ROWS = 1_200_000
 
 #: batches of the batched screen that held a query quantised to zeros and were
 #: answered by the bf16 search (a process-wide counter)
@@ -664,6 +667,33 @@ def q8_cnorm(rows: torch.Tensor) -> torch.Tensor:
     return out
 
 
+#: most stages of the batched screen's main launch (knn_plan.h Q8_MAX_STAGES)
+Q8_MAX_STAGES = 4
+
+
+def _q8_stages_arg(stages: Optional[int]) -> int:
+    """``stages`` as the extension takes it: 0 for None (the plan's rule)."""
+    if stages is None:
+        return 0
+    n = int(stages)
+    if not 1 <= n <= Q8_MAX_STAGES:
+        raise ValueError(f"stages must be in [1, {Q8_MAX_STAGES}] or None, got {stages}")
+    return n
+
+
+def q8_stage_plan(B: int, N: int, k: int, stages: Optional[int] = None):
+    """The stage plan of the batched screen for a request of ``B`` queries over
+    ``N`` rows (knn_plan.h ``plan_q8_stages``; host only, no GPU needed): a
+    dict with ``first`` (n + 1 bounds in 256-row tiles: stage i scans the rows
+    ``[256 * first[i], min(N, 256 * first[i + 1]))``), ``chunk_tiles`` and
+    ``nchunks`` (n each: the stage's launch geometry). ``first[0]`` rows are
+    left to the prepass sample."""
+    first, chunk_tiles, nchunks = _require_ext().q8_stage_plan(
+        int(B), int(N), min(int(k), KMAX), _q8_stages_arg(stages)
+    )
+    return dict(first=list(first), chunk_tiles=list(chunk_tiles), nchunks=list(nchunks))
+
+
 def q8_screen_probe(
     queries: torch.Tensor,
     corpus: torch.Tensor,
@@ -713,7 +743,9 @@ def cosine_topk_q8(
     batch_min_b: Optional[int] = None,
     cap: Optional[int] = None,
     batch_min_rows: Optional[int] = None,
-) -> Tuple[torch.Tensor, torch.Tensor]:
+    stages: Optional[int] = None,
+    return_counts: bool = False,
+):
     """``cosine_topk`` (``cosine_topk_filtered`` when ``labels``/``want`` are
     given) that reads the int8 mirror of the corpus where the request is one
     of the streaming small-batch kernel's (``q8_in_plan``): the scan over all
@@ -738,7 +770,15 @@ def cosine_topk_q8(
     the mirror's largest row norm (``quantize_rows_q8``); None computes it
     from ``corpus`` on every call. ``cap`` overrides the per-query candidate
     capacity of that path (tests). A batch holding a query that quantises to
-    zeros is answered by the bf16 search (``q8_degenerate_fallbacks``)."""
+    zeros is answered by the bf16 search (``q8_degenerate_fallbacks``).
+
+    The screen runs its main launch in stages and raises each query's floor
+    between them to the k-th best exact score found so far (knn_plan.h
+    ``plan_q8_stages``): later stages pass fewer candidates and the result is
+    the same. ``stages`` forces their number (1: one launch; up to
+    ``Q8_MAX_STAGES``); None leaves it to KAKVEDA_Q8_STAGES, else to the
+    plan's rule. ``return_counts`` (GPU only) adds a third result: the
+    candidates per query (i32 [B]; empty where the request is not screened)."""
     global q8_overflow_fallbacks, q8_degenerate_fallbacks
     _q8_check_dim(int(queries.shape[1]))
     if (labels is None) != (want is None):
@@ -769,14 +809,17 @@ def cosine_topk_q8(
     ):
         if cnorm is None:
             cnorm = q8_cnorm(corpus[:n])
-        filt.update(cnorm=cnorm, batch_min_b=min_b, cap=int(cap or 0))
-    scores, idx, fallback, _counts = ext.cosine_topk_q8(
+        filt.update(cnorm=cnorm, batch_min_b=min_b, cap=int(cap or 0),
+                    stages=_q8_stages_arg(stages))
+    scores, idx, fallback, counts = ext.cosine_topk_q8(
         queries, corpus, codes, meta, kk, n, **filt
     )
     q8_overflow_fallbacks += int(fallback == 1)
     q8_degenerate_fallbacks += int(fallback == 2)
     if want is not None:
         scores = torch.where(idx < 0, torch.full_like(scores, float("-inf")), scores)
+    if return_counts:
+        return _pad_topk(scores, idx, k) + (counts,)
     return _pad_topk(scores, idx, k)
 
 

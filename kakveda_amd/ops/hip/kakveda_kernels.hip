@@ -515,24 +515,52 @@ void quantize_rows_q8(torch::Tensor rows, torch::Tensor out_codes,
 namespace {
 
 // The batched int8 screen (q8_screen_impl.h) up to and including the rescore:
-// quantise the queries, the unchanged floors and seeds, T_r and kappa, the
-// screen over the codes, emit_bin, then the bf16 scores of every emitted
-// entry. Afterwards e.cand / e.ccount hold what the bf16 emission launch
-// leaves there plus the screen's false positives, all with bf16 scores.
+// quantise the queries, the unchanged floors and seeds, T_r and kappa, then
+// per stage of the plan (knn_plan.h plan_q8_stages) the screen over the
+// stage's codes, emit_bin and the bf16 scores of every entry the stage
+// emitted, and between two stages the floor refresh (emit_merge_topk into a
+// scratch top-k, q8_refresh_floor). Everything runs on the one stream with no
+// host synchronisation; a stage's record segments are consumed by its
+// emit_bin before the next stage writes them. Afterwards e.cand / e.ccount
+// hold every column of the exact top-k (q8_plan.h "Staged floors"), all with
+// bf16 scores; with one stage, exactly what the bf16 emission launch leaves
+// there plus the screen's false positives.
 struct Q8Screen {
   EmitBufs e;
   torch::Tensor first;      // i32 [B]: entries seeded before the screen
-  torch::Tensor thrT;       // f32 [B]: T_r
+  torch::Tensor thrT;       // f32 [B]: T_r (of the last stage)
   torch::Tensor small;      // i32 [2]: bits of kappa, degenerate rows
-  torch::Tensor rowthr;     // u32 [B]: the prepass floors, order-encoded
+  torch::Tensor rowthr;     // u32 [B]: the floors, order-encoded (one stage:
+                            // the prepass floors)
   torch::Tensor before;     // the candidate buffer ahead of the rescore (probe)
   long cap, seg;
+  StagePlan sp;
 };
+
+// The stage plan of a request. The boundary search of plan_q8_stages costs a
+// few hundred chunkings; a serving process asks for the same few shapes over
+// and over, so the last plan is kept per thread.
+StagePlan q8_stage_plan(const KnnArgs& a, const KnnPlan& p, const KnnEnv& env,
+                        int k, int64_t stages) {
+  TORCH_CHECK(stages >= 0 && stages <= Q8_MAX_STAGES,
+              "stages must be in [1,", Q8_MAX_STAGES, "], or 0 for the plan's rule");
+  const int want = stages > 0 ? (int)stages : env.q8_stages;
+  struct Key {
+    int B, N, k, want;
+  };
+  thread_local Key key{-1, -1, -1, -1};
+  thread_local StagePlan memo;
+  if (key.B != a.B || key.N != a.N || key.k != k || key.want != want) {
+    memo = plan_q8_stages(p, env, want);
+    key = Key{a.B, a.N, k, want};
+  }
+  return memo;
+}
 
 Q8Screen run_q8_screen(const KnnArgs& a, const KnnPlan& p, const KnnEnv& env,
                        const torch::Tensor& codes, const torch::Tensor& meta,
                        const torch::Tensor& cnorm, long cap_override,
-                       bool keep_before) {
+                       bool keep_before, int k, int64_t stages) {
   const auto i8 = torch::TensorOptions().dtype(torch::kInt8).device(a.dev);
   auto qcodes = torch::empty({(long)a.B, (long)a.D}, i8);
   auto qmeta = torch::empty({(long)a.B, 2L}, a.f32());
@@ -543,9 +571,15 @@ Q8Screen run_q8_screen(const KnnArgs& a, const KnnPlan& p, const KnnEnv& env,
   const Floors f = run_emission_floors(a, p.pre_grid, p.pre_tiles,
                                        p.prepass_mode, KMAX);
   Q8Screen s;
+  s.sp = q8_stage_plan(a, p, env, k, stages);
+  const StagePlan& sp = s.sp;
   s.rowthr = f.rowthr;
   s.cap = cap_override > 0 ? cap_override : p.cap;
-  s.seg = emit_seg_cap(a.B, s.cap, p.mch, env.seg);
+  // one set of record segments, for the stage with the most blocks
+  Chunking widest = sp.ch[0];
+  for (int i = 1; i < sp.n; ++i)
+    if (sp.ch[i].nchunks > widest.nchunks) widest = sp.ch[i];
+  s.seg = emit_seg_cap(a.B, s.cap, widest, env.seg);
   s.thrT = torch::empty({(long)a.B}, a.f32());
   s.small = torch::zeros({2L}, a.i32());
   hipLaunchKernelGGL(q8_screen_prep, dim3((a.B + 3) / 4), dim3(256), 0, a.stream,
@@ -556,29 +590,64 @@ Q8Screen run_q8_screen(const KnnArgs& a, const KnnPlan& p, const KnnEnv& env,
                      s.thrT.data_ptr<float>(), (float*)s.small.data_ptr<int>(),
                      s.small.data_ptr<int>() + 1);
   const bool seeded = p.skip_tiles > 0;
-  s.e = new_emit_bufs(a, s.cap, p.mch, s.seg, seeded ? &f : nullptr);
-  s.first = s.e.ccount.clone();
+  s.e = new_emit_bufs(a, s.cap, widest, s.seg, seeded ? &f : nullptr);
+  // firsts[i]: the rows' counts ahead of stage i (row 0: the seeds)
+  auto firsts = torch::empty({(long)sp.n, (long)a.B}, a.i32());
+  s.first = firsts[0];
+  torch::Tensor best_s, best_i;
+  if (sp.n > 1) {
+    best_s = torch::empty({(long)a.B, (long)k}, a.f32());
+    best_i = torch::empty({(long)a.B, (long)k}, a.i64());
+  }
   unsigned long long* const eseg = (unsigned long long*)s.e.eseg.data_ptr<int64_t>();
   unsigned* const esegcnt = (unsigned*)s.e.esegcnt.data_ptr<int>();
   unsigned long long* const cand = (unsigned long long*)s.e.cand.data_ptr<int64_t>();
   unsigned* const ccount = (unsigned*)s.e.ccount.data_ptr<int>();
-  const dim3 grid(p.mch.nchunks, p.mch.row_tiles);
-  hipLaunchKernelGGL(cosine_topk_screen8p_i8, grid, dim3(THREADS8), 0, a.stream,
-                     (const signed char*)qcodes.data_ptr<int8_t>(),
-                     (const signed char*)codes.data_ptr<int8_t>(),
-                     (const float*)meta.data_ptr<float>(),
-                     (const float*)s.thrT.data_ptr<float>(),
-                     (const float*)s.small.data_ptr<int>(), a.B, a.N, a.D,
-                     p.mch.chunk_tiles, p.mch.nchunks, eseg, esegcnt, s.seg,
-                     p.skip_tiles);
-  hipLaunchKernelGGL(emit_bin, grid, dim3(256), 0, a.stream,
-                     (const unsigned long long*)eseg, (const unsigned*)esegcnt,
-                     (int)s.seg, p.mch.chunk_tiles, p.mch.nchunks, a.B, a.N, cand,
-                     ccount, s.cap, p.skip_tiles);
-  if (keep_before) s.before = s.e.cand.clone();
-  hipLaunchKernelGGL(q8_rescore_mfma, dim3(8, a.B), dim3(256), 0, a.stream, a.q,
-                     a.c, a.N, a.D, cand, (const unsigned*)ccount,
-                     (const unsigned*)s.first.data_ptr<int>(), s.cap);
+  for (int i = 0; i < sp.n; ++i) {
+    const Chunking& ch = sp.ch[i];
+    unsigned* const first = (unsigned*)firsts[i].data_ptr<int>();
+    C10_HIP_CHECK(hipMemcpyAsync(first, ccount, (size_t)a.B * sizeof(unsigned),
+                                 hipMemcpyDeviceToDevice, a.stream));
+    // the stage ends where the next begins: the kernel clamps its loads to
+    // n_end - 1 and drops columns at or past n_end, as it does at the corpus end
+    const int n_end = (int)std::min((long)a.N, (long)sp.first[i + 1] * BN8);
+    const dim3 grid(ch.nchunks, ch.row_tiles);
+    hipLaunchKernelGGL(cosine_topk_screen8p_i8<true>, grid, dim3(THREADS8), 0,
+                       a.stream, (const signed char*)qcodes.data_ptr<int8_t>(),
+                       (const signed char*)codes.data_ptr<int8_t>(),
+                       (const float*)meta.data_ptr<float>(),
+                       (const float*)s.thrT.data_ptr<float>(),
+                       (const float*)s.small.data_ptr<int>(), a.B, n_end, a.D,
+                       ch.chunk_tiles, ch.nchunks, eseg, esegcnt, s.seg,
+                       sp.first[i]);
+    hipLaunchKernelGGL(emit_bin, grid, dim3(256), 0, a.stream,
+                       (const unsigned long long*)eseg, (const unsigned*)esegcnt,
+                       (int)s.seg, ch.chunk_tiles, ch.nchunks, a.B, n_end, cand,
+                       ccount, s.cap, sp.first[i]);
+    if (keep_before && i == 0) s.before = s.e.cand.clone();
+    hipLaunchKernelGGL(q8_rescore_mfma, dim3(8, a.B), dim3(256), 0, a.stream, a.q,
+                       a.c, a.N, a.D, cand, (const unsigned*)ccount,
+                       (const unsigned*)first, s.cap);
+    if (env.emit_debug)
+      printf("q8 screen: stage %d/%d tiles [%d, %d) chunks=%d x %d tiles "
+             "segments max=%d mean/row=%.1f\n",
+             i + 1, sp.n, sp.first[i], sp.first[i + 1], ch.nchunks,
+             ch.chunk_tiles,
+             s.e.esegcnt.slice(0, 0, (long)ch.nchunks * ch.row_tiles)
+                 .max().item<int>(),
+             (s.e.ccount - firsts[i]).to(torch::kFloat32).mean().item<float>());
+    if (i + 1 == sp.n) break;
+    hipLaunchKernelGGL(emit_merge_topk, dim3(a.B), dim3(256), 0, a.stream,
+                       (const unsigned long long*)cand, (const unsigned*)ccount,
+                       best_s.data_ptr<float>(),
+                       (long*)best_i.data_ptr<int64_t>(), a.B, s.cap, k);
+    hipLaunchKernelGGL(q8_refresh_floor, dim3((a.B + 255) / 256), dim3(256), 0,
+                       a.stream, (const float*)best_s.data_ptr<float>(), k,
+                       (const float*)qmeta.data_ptr<float>(),
+                       (const float*)cnorm.data_ptr<float>(), a.B, a.D,
+                       (unsigned*)s.rowthr.data_ptr<int>(),
+                       s.thrT.data_ptr<float>());
+  }
   C10_HIP_KERNEL_LAUNCH_CHECK();
   return s;
 }
@@ -606,12 +675,15 @@ bool q8_screen_in_plan(const KnnArgs& a, const KnnPlan& p, const KnnEnv& env,
 // as it is. Returns (scores, idx, fallback, counts): fallback is 1 when the
 // candidates overflowed (`cap` > 0 overrides their per-row capacity on the
 // batched path), 2 when a query of the batch quantised to zeros, 0 otherwise;
-// counts are the per-query stage-1 candidate counts (empty off-plan).
+// counts are the per-query stage-1 candidate counts (empty off-plan). `stages`
+// forces the stage count of the batched screen (0: KAKVEDA_Q8_STAGES, else
+// the plan's rule).
 std::tuple<torch::Tensor, torch::Tensor, int64_t, torch::Tensor> cosine_topk_q8(
     torch::Tensor queries, torch::Tensor corpus, torch::Tensor codes,
     torch::Tensor meta, int64_t k, int64_t valid_n,
     c10::optional<torch::Tensor> labels, c10::optional<torch::Tensor> want,
-    c10::optional<torch::Tensor> cnorm, int64_t batch_min_b, int64_t cap) {
+    c10::optional<torch::Tensor> cnorm, int64_t batch_min_b, int64_t cap,
+    int64_t stages) {
   const Q8Checked c =
       check_q8_search(queries, corpus, codes, meta, k, valid_n, labels, want);
   TORCH_CHECK(queries.size(1) % BK == 0, "D must be a multiple of ", BK);
@@ -624,7 +696,8 @@ std::tuple<torch::Tensor, torch::Tensor, int64_t, torch::Tensor> cosine_topk_q8(
     TORCH_CHECK(plan_fits_grid(p, a.B), "cosine_topk_q8: ", a.B,
                 " query rows need more row tiles than one launch holds; split "
                 "the batch");
-    Q8Screen s = run_q8_screen(a, p, env, codes, meta, *cnorm, cap, false);
+    Q8Screen s = run_q8_screen(a, p, env, codes, meta, *cnorm, cap, false,
+                               (int)k, stages);
     auto out_score = torch::empty({a.B, k}, a.f32());
     auto out_idx = torch::empty({a.B, k}, a.i64());
     hipLaunchKernelGGL(emit_merge_topk, dim3(a.B), dim3(256), 0, a.stream,
@@ -639,9 +712,8 @@ std::tuple<torch::Tensor, torch::Tensor, int64_t, torch::Tensor> cosine_topk_q8(
       printf("q8 screen: rows=%d max=%ld mean=%.1f cap=%ld degenerate=%d%s\n",
              a.B, mx, s.e.ccount.to(torch::kFloat32).mean().item<float>(), s.cap,
              degen, mx > s.cap ? "  FALLBACK" : "");
-      printf("q8 screen: segments=%ld max=%d seg=%ld skip_tiles=%d\n",
-             (long)s.e.esegcnt.size(0), s.e.esegcnt.max().item<int>(), s.seg,
-             p.skip_tiles);
+      printf("q8 screen: segments=%ld seg=%ld skip_tiles=%d stages=%d\n",
+             (long)s.e.esegcnt.size(0), s.seg, p.skip_tiles, s.sp.n);
     }
     if (degen > 0 || mx > s.cap) {
       auto [sc, ix] = cosine_topk_impl(queries, corpus, (int)k, c.N, env, true);
@@ -697,9 +769,33 @@ std::vector<torch::Tensor> q8_screen_probe(
   const KnnPlan p = plan_cosine_topk(a.B, c.N, (int)k, env, true, false);
   TORCH_CHECK(q8_screen_in_plan(a, p, env, false, 1) && plan_fits_grid(p, a.B),
               "q8_screen_probe: not a request of the batched int8 screen");
-  Q8Screen s = run_q8_screen(a, p, env, codes, meta, cnorm, cap, true);
+  // one stage: what it returns keeps its meaning (the prepass floors, one T_r)
+  Q8Screen s = run_q8_screen(a, p, env, codes, meta, cnorm, cap, true, (int)k, 1);
   return {s.e.ccount, s.first, s.before, s.e.cand, s.thrT,
           s.small.slice(0, 0, 1).view(torch::kFloat32), s.rowthr};
+}
+
+// The stage plan of the batched screen for (B, N, k, stages) under this
+// process's environment: (first [n + 1], chunk_tiles [n], nchunks [n]); stage
+// i scans the 256-column tiles [first[i], first[i + 1]). Host only.
+std::tuple<std::vector<int64_t>, std::vector<int64_t>, std::vector<int64_t>>
+q8_stage_plan_op(int64_t B, int64_t N, int64_t k, int64_t stages) {
+  static const KnnEnv env = parse_knn_env(std::getenv);
+  TORCH_CHECK(B >= 1 && N >= 1 && N <= 0x7fffffffL && k >= 1 && k <= KMAX,
+              "q8_stage_plan: B, N or k out of range");
+  TORCH_CHECK(stages >= 0 && stages <= Q8_MAX_STAGES,
+              "stages must be in [1,", Q8_MAX_STAGES, "], or 0 for the plan's rule");
+  const KnnPlan p = plan_cosine_topk((int)B, (int)N, (int)k, env, true, false);
+  TORCH_CHECK(p.main == MainKernel::Emit8p && p.prepass,
+              "q8_stage_plan: not a request of the batched int8 screen");
+  const StagePlan sp =
+      plan_q8_stages(p, env, stages > 0 ? (int)stages : env.q8_stages);
+  std::vector<int64_t> first(sp.first, sp.first + sp.n + 1), ct, nc;
+  for (int i = 0; i < sp.n; ++i) {
+    ct.push_back(sp.ch[i].chunk_tiles);
+    nc.push_back(sp.ch[i].nchunks);
+  }
+  return {first, ct, nc};
 }
 
 // Benchmark probe: the stage-1 candidate counts of one request under both
@@ -935,6 +1031,68 @@ double probe8p(torch::Tensor queries, torch::Tensor corpus, int64_t mode,
   hipEventElapsedTime(&ms, e0, e1);
   hipEventDestroy(e0);
   hipEventDestroy(e1);
+  return (double)ms / (double)iters;
+}
+
+double probe8p_i8(torch::Tensor queries, torch::Tensor codes, torch::Tensor meta,
+                  int64_t mode, int64_t iters) {
+  // Timing probe of the int8 screen kernel, the twin of probe8p: mode 1 = no
+  // epilogue (cosine_topk_screen8p_i8<false>: staging, int8 MFMA, waits, barriers
+  // only), 12 = the production kernel under T_r = +big (accumulator
+  // conversion and hot sweep on every tile, the cold path never taken). Both
+  // run the whole-corpus geometry of probe8p over the mirror's rows and emit
+  // nothing. Returns ms per launch.
+  check_bf16_2d(queries, "queries");
+  TORCH_CHECK(mode == 1 || mode == 12,
+              "probe8p_i8 mode must be 1 (GEMM core) or 12 (hot sweep), got ", mode);
+  TORCH_CHECK(iters >= 1, "iters must be positive");
+  const int64_t N = codes.size(0), D = queries.size(1);
+  TORCH_CHECK(q8_screen_dim_ok(D), "D must be a multiple of ", Q8_SEG, " up to ",
+              Q8_SCREEN_MAX_D);
+  TORCH_CHECK(N >= 1 && N <= 0x7fffffffL, "rows out of range");
+  check_q8_mirror(codes, meta, queries.device(), N, D);
+  const KnnArgs a{(const bf16_t*)queries.data_ptr(), nullptr, (int)queries.size(0),
+                  (int)N, (int)D, c10::hip::getCurrentHIPStream().stream(),
+                  queries.device()};
+  const Chunking ch = chunking(a.B, a.N, BM8, default_target(BM8));
+  TORCH_CHECK(ch.row_tiles <= MAX_GRID_Y, "too many query rows for one launch");
+  const auto i8 = torch::TensorOptions().dtype(torch::kInt8).device(a.dev);
+  auto qcodes = torch::empty({(long)a.B, (long)a.D}, i8);
+  auto qmeta = torch::empty({(long)a.B, 2L}, a.f32());
+  hipLaunchKernelGGL(q8_quantize_kernel, dim3((a.B + 31) / 32), dim3(256), 0,
+                     a.stream, a.q, (long)a.B, a.D,
+                     (signed char*)qcodes.data_ptr<int8_t>(),
+                     qmeta.data_ptr<float>(), 0L);
+  auto thrT = torch::full({(long)a.B}, 1e38f, a.f32());
+  auto kappa = torch::ones({1L}, a.f32());
+  const long blocks = (long)ch.nchunks * ch.row_tiles;
+  auto eseg = torch::empty({blocks}, a.i64());  // one record a segment, unused
+  auto esegcnt = torch::empty({blocks}, a.i32());
+  const auto kernel =
+      mode == 1 ? cosine_topk_screen8p_i8<false> : cosine_topk_screen8p_i8<true>;
+  auto launch = [&] {
+    hipLaunchKernelGGL(kernel, dim3(ch.nchunks, ch.row_tiles), dim3(THREADS8), 0,
+                       a.stream, (const signed char*)qcodes.data_ptr<int8_t>(),
+                       (const signed char*)codes.data_ptr<int8_t>(),
+                       (const float*)meta.data_ptr<float>(),
+                       (const float*)thrT.data_ptr<float>(),
+                       (const float*)kappa.data_ptr<float>(), a.B, a.N, a.D,
+                       ch.chunk_tiles, ch.nchunks,
+                       (unsigned long long*)eseg.data_ptr<int64_t>(),
+                       (unsigned*)esegcnt.data_ptr<int>(), 1L, 0);
+  };
+  launch();  // warmup
+  hipEvent_t e0, e1;
+  C10_HIP_CHECK(hipEventCreate(&e0));
+  C10_HIP_CHECK(hipEventCreate(&e1));
+  C10_HIP_CHECK(hipEventRecord(e0, a.stream));
+  for (long i = 0; i < iters; ++i) launch();
+  C10_HIP_CHECK(hipEventRecord(e1, a.stream));
+  C10_HIP_CHECK(hipEventSynchronize(e1));
+  float ms = 0.f;
+  C10_HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
+  C10_HIP_CHECK(hipEventDestroy(e0));
+  C10_HIP_CHECK(hipEventDestroy(e1));
   return (double)ms / (double)iters;
 }
 
@@ -1433,7 +1591,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("want") = pybind11::none(),
         pybind11::arg("cnorm") = pybind11::none(),
         pybind11::arg("batch_min_b") = (int64_t)0,
-        pybind11::arg("cap") = (int64_t)0);
+        pybind11::arg("cap") = (int64_t)0, pybind11::arg("stages") = (int64_t)0);
+  m.def("q8_stage_plan", &q8_stage_plan_op,
+        "stage plan of the batched int8 screen: tile bounds and chunkings",
+        pybind11::arg("B"), pybind11::arg("N"), pybind11::arg("k"),
+        pybind11::arg("stages") = (int64_t)0);
   m.def("q8_screen_probe", &q8_screen_probe,
         "batched int8 screen: candidate lists before and after the rescore",
         pybind11::arg("queries"), pybind11::arg("corpus"), pybind11::arg("codes"),
@@ -1451,6 +1613,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("kmeans_assign", &kmeans_assign,
         "argmax-cosine assignment, LDS-resident centroids (C<=64)");
   m.def("probe8p", &probe8p, "8p epilogue-isolation timing probe");
+  m.def("probe8p_i8", &probe8p_i8, "int8 screen epilogue-isolation timing probe",
+        pybind11::arg("queries"), pybind11::arg("codes"), pybind11::arg("meta"),
+        pybind11::arg("mode"), pybind11::arg("iters"));
   m.def("floor_probe", &floor_probe, "emission floor pipeline debug probe",
         pybind11::arg("queries"), pybind11::arg("corpus"),
         pybind11::arg("pregq"), pybind11::arg("k") = (int64_t)KMAX,

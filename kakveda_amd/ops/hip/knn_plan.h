@@ -5,6 +5,7 @@
 #pragma once
 
 #include <algorithm>
+#include <cmath>
 #include <cstdlib>
 #include <stdexcept>
 #include <string>
@@ -41,6 +42,7 @@ struct KnnEnv {
   bool skip_sample = true;       // KAKVEDA_KNN_SKIP_SAMPLE: 1 (default), 0
   int pre_tiles = 0;             // KAKVEDA_KNN_PRE_TILES (0: the plan's rule)
   bool q8_batch = true;          // KAKVEDA_Q8_BATCH: 1 (default), 0
+  int q8_stages = 0;             // KAKVEDA_Q8_STAGES (0: the plan's rule)
 };
 
 // A forced size of the compact prepass's blocks, in column tiles (the
@@ -115,6 +117,15 @@ KnnEnv parse_knn_env(GetEnv&& get) {
                              "' is not a setting; accepted: 1 (default: "
                              "cosine_topk_q8 screens batches with int8), 0 (it "
                              "answers them with the bf16 search)");
+  v = get("KAKVEDA_Q8_STAGES");
+  const std::string qs = v ? v : "";
+  if (qs == "1" || qs == "2" || qs == "3" || qs == "4") e.q8_stages = qs[0] - '0';
+  else if (!qs.empty())
+    throw std::runtime_error("KAKVEDA_Q8_STAGES='" + qs +
+                             "' is not a setting; accepted: 1 (the batched int8 "
+                             "screen runs one main launch), 2, 3, 4 (it "
+                             "refreshes its floors between that many stages), "
+                             "or unset for the plan's rule");
   return e;
 }
 
@@ -272,6 +283,112 @@ inline void main_geometry(KnnPlan& p, int B, const KnnEnv& env) {
                      env.target > 0 ? env.target : default_target(BM8)),
       p.ch);
   p.mseg = emit_seg_cap(B, env.cap, p.mch, env.seg);
+}
+
+// ---------------------------------------------------------------------------
+// Stage plan of the batched int8 screen (kakveda_kernels.hip run_q8_screen).
+//
+// The screen's floors come from the prepass sample, a prefix of S columns;
+// a floor taken from a prefix of P columns lets about k * (N - P) / P of the
+// other columns through. The main launch over [skip_tiles, ntiles) is
+// therefore cut into n stages [first[i], first[i + 1]) and the floors are
+// refreshed between them from the exact scores found so far, so stage i
+// screens against a floor taken from the prefix first[i]. With boundaries
+// geometric in the prefix, first[i] ~ P0 * (ntiles / P0)^(i / n), every stage
+// lets the same share through and the candidates fall from (N - P0) / P0 to
+// n * ((N / P0)^(1 / n) - 1) in units of k (stage_model_count): 37 -> 10.4 ->
+// 7.1 -> 5.9 for n = 1..4 at N / P0 = 38, the bench shape.
+//
+// P0 is skip_tiles, or the sample's tile count when nothing is skipped. Where
+// that leaves no room (the sample covers the corpus) the stages split
+// [0, ntiles) evenly. Each stage is chunked like the single launch, by
+// balanced_chunking over its own tiles, and each interior boundary is moved
+// by up to 1/64 of its value to where the stage to its right wastes the
+// fewest block slots in its last round (right to left: the last stage is the
+// longest, the first takes the remainder).
+//
+// n: `stages` > 0 forces it (KAKVEDA_Q8_STAGES, the op's argument), clamped to
+// Q8_MAX_STAGES and to one tile per stage; 0 asks for Q8_STAGES_DEFAULT,
+// reduced while the shortest stage is less than one full round of 256 blocks
+// of 4 tiles (Q8_STAGE_MIN_WORK tile-blocks): below that a stage cannot fill
+// the GPU once, and its boundary costs a drained GPU and four small launches.
+// n = 1 is the single launch over p.mch, field for field.
+// Measured (profiles/q8_staged_floors.md, 10M x 768, B = 2048, k = 5): 26.16,
+// 20.76, 20.31 and 19.94 ms a bench step for n = 1..4, 2,150 -> 289 candidates
+// a row at n = 4, hence the default; n = 4 also wins on the 2.5M and 1.25M
+// shards, whose shortest stages are 3,376 and 2,200 tile-blocks. The
+// Q8_STAGE_MIN_WORK floor itself is the reasoning above, not a measurement.
+// ---------------------------------------------------------------------------
+constexpr int Q8_MAX_STAGES = 4;
+constexpr int Q8_STAGES_DEFAULT = 4;
+constexpr long Q8_STAGE_MIN_WORK = 256L * 4;
+
+struct StagePlan {
+  int n;
+  int prefix;                    // P0, in column tiles
+  int first[Q8_MAX_STAGES + 1];  // stage i scans tiles [first[i], first[i+1])
+  Chunking ch[Q8_MAX_STAGES];
+};
+
+// Interior boundary i of n before any nudge (see above).
+inline int stage_boundary(int hi, int prefix, int i, int n) {
+  if (prefix >= hi) return (int)((long)hi * i / n);
+  return (int)std::lround(prefix * std::pow((double)hi / prefix, (double)i / n));
+}
+
+inline StagePlan plan_q8_stages(const KnnPlan& p, const KnnEnv& env, int stages) {
+  const int lo = p.skip_tiles, hi = p.ch.ntiles;
+  const int sampled = p.preg * (PRE_TILES * BN / BN8);
+  StagePlan s{};
+  s.prefix = std::max(1, lo > 0 ? lo : sampled);
+  int n = stages > 0 ? std::min(stages, Q8_MAX_STAGES) : Q8_STAGES_DEFAULT;
+  n = std::max(1, std::min(n, hi - lo));
+  if (stages <= 0)
+    while (n > 1 && (long)(stage_boundary(hi, s.prefix, 1, n) - lo) *
+                            p.ch.row_tiles < Q8_STAGE_MIN_WORK)
+      --n;
+  s.n = n;
+  s.first[0] = lo;
+  s.first[n] = hi;
+  if (n == 1) {
+    s.ch[0] = p.mch;
+    return s;
+  }
+  const long target = env.target > 0 ? env.target : default_target(BM8);
+  auto stage_chunking = [&](int tiles) {
+    return balanced_chunking(chunking_tiles(p.ch.row_tiles, tiles, target), p.ch);
+  };
+  for (int i = n - 1; i >= 1; --i) {
+    const int next = s.first[i + 1];
+    // stages 0..i-1 and stage i keep at least one tile each
+    const int tmin = lo + i, tmax = next - 1;
+    const int g = std::max(tmin, std::min(stage_boundary(hi, s.prefix, i, n), tmax));
+    const int w = g / 64;
+    int best = g;
+    long best_waste = -1;
+    for (int t = std::max(tmin, g - w); t <= std::min(tmax, g + w); ++t) {
+      const long waste = model_makespan(stage_chunking(next - t)) * 256 -
+                         (long)(next - t) * p.ch.row_tiles;
+      if (best_waste < 0 || waste < best_waste ||
+          (waste == best_waste && std::abs(t - g) < std::abs(best - g))) {
+        best = t;
+        best_waste = waste;
+      }
+    }
+    s.first[i] = best;
+  }
+  for (int i = 0; i < n; ++i) s.ch[i] = stage_chunking(s.first[i + 1] - s.first[i]);
+  return s;
+}
+
+// Modelled candidates per row in units of the floor depth k: stage i lets
+// (its columns) / (the prefix its floors were taken from) through.
+inline double stage_model_count(const StagePlan& s) {
+  double c = 0.0;
+  for (int i = 0; i < s.n; ++i)
+    c += (double)(s.first[i + 1] - s.first[i]) /
+         (double)(i == 0 ? s.prefix : s.first[i]);
+  return c;
 }
 
 // Blocks of the 128x128 kernel resident at once: 2 per CU (its 80 KiB of

@@ -112,6 +112,20 @@ Q8_HD float q8_slack(int D) { return (float)D * 0x1p-22f; }
 // unit rows: under 2^-21 in score units against the D * 2^-23 >= 2^-16 the
 // second half of q8_slack leaves for them. A query with sq_r == 0 (stored as
 // zeros) has no T_r: a batch that holds one takes the bf16 path.
+//
+// Staged floors (knn_plan.h plan_q8_stages, q8_refresh_floor). The main launch
+// runs as stages over disjoint column ranges, and between two stages floor_r
+// is raised to the k-th best bf16 score among the entries row r holds so far
+// (seeds and rescored candidates; k is the request's). The result stays exact:
+// let s_k be the k-th best bf16 score of row r over the whole corpus. Any k
+// columns score at most as well as the best k, so the k-th best of ANY subset
+// of the columns is <= s_k: every floor a stage reads, the prepass's included,
+// is <= s_k. A column of the final top-k scores >= s_k >= that floor, so by
+// the argument above it is a candidate of the stage that scans it (or a seed)
+// and is rescored. The test is >=, so columns tied with the floor are still
+// emitted and the merge breaks the tie by column as before. Stages are
+// disjoint and the seeds lie ahead of the first, so no pair is entered twice.
+// A row with fewer than k entries, or past its capacity, raises nothing.
 // ---------------------------------------------------------------------------
 constexpr int Q8_SCREEN_MAX_D = 1024;  // 1024 * 127^2 < 2^24 <= 1152 * 127^2
 

@@ -4,7 +4,9 @@
 //
 //   q8_cnorm_kernel          largest row norm of the quantised rows (ingest)
 //   q8_screen_prep           per query row: T_r, kappa's term, degenerate flag
+//   q8_refresh_floor         between stages: raise the floors, recompute T_r
 //   cosine_topk_screen8p_i8  the mode-9 emission kernel over int8 codes
+//                            (<false>: without its epilogue, a timing probe)
 //   q8_rescore_mfma          bf16 scores of the candidates, bit-equal to the
 //                            bf16 emission kernel's
 #pragma once
@@ -93,6 +95,35 @@ __global__ __launch_bounds__(256) void q8_screen_prep(
             __float_as_uint(q8_screen_kappa(q8_code_norm(sq, ss, D), sq)));
 }
 
+// ---------------------------------------------------------------------------
+// Floor refresh between two stages of the screen (knn_plan.h plan_q8_stages;
+// why it stays exact: q8_plan.h "Staged floors"). best_s [B, k] is
+// emit_merge_topk's output over every entry the row holds so far, seeds
+// included, all with bf16 scores: its last column is the row's k-th best
+// exact score. Where that is above the floor, the floor is raised to it;
+// T_r is recomputed from the floor in both cases (a degenerate row keeps its
+// +big). A row with fewer than k entries, and a row past its capacity (the
+// merge wrote no scores for it), reads NEG_INF and raises nothing. kappa and
+// the degenerate count do not depend on the floors and stay. One thread per
+// row.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void q8_refresh_floor(
+    const float* __restrict__ best_s, int k, const float* __restrict__ qmeta,
+    const float* __restrict__ cnorm, int B, int D,
+    unsigned* __restrict__ rowthr, float* __restrict__ thrT) {
+  const int r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= B) return;
+  unsigned fl = rowthr[r];
+  const float kth = best_s[(size_t)r * k + (k - 1)];
+  if (kth > NEG_INF && enc_f32(kth) > fl) {
+    fl = enc_f32(kth);
+    rowthr[r] = fl;
+  }
+  const float sq = qmeta[2 * r], errq = qmeta[2 * r + 1];
+  if (sq > 0.0f)
+    thrT[r] = q8_screen_threshold(dec_f32(fl), sq, errq, *cnorm, D);
+}
+
 // 16 codes of a staged row: the int8 reading of read_frag's 16 bytes.
 DEVINL i32x4 read_frag_i8(const char* lds_tile, int row, int slot) {
   const int s_phys = slot ^ (row & 7);
@@ -135,7 +166,14 @@ DEVINL void glds4(const void* gsrc, void* lds_dst) {
 // staging image, stash and the cursor (SCREEN_META_OFF).
 // Columns past N - 1 read the pair of column N - 1; the cold path drops them
 // as the parent does.
+//
+// EPILOGUE = true is the production kernel. EPILOGUE = false is the timing
+// probe (probe8p_i8 mode 1, the int8 twin of cosine_topk_partial8p_t<1>): the
+// same schedule with everything behind the K loop compiled out. It keeps the
+// staging, the (scale, err) loads and every wait and barrier, pins the
+// accumulators, and writes one zero count per segment and nothing else.
 // ---------------------------------------------------------------------------
+template <bool EPILOGUE>
 __global__ __launch_bounds__(THREADS8, 2) void cosine_topk_screen8p_i8(
     const signed char* __restrict__ Q, const signed char* __restrict__ C,
     const float* __restrict__ meta, const float* __restrict__ thrT,
@@ -325,6 +363,14 @@ __global__ __launch_bounds__(THREADS8, 2) void cosine_topk_screen8p_i8(
     }
     // group 0's make-up barrier pairs with group 1's last phase barrier
     if (wr == 0 && j == tiles_here - 1) __builtin_amdgcn_s_barrier();
+
+    if constexpr (!EPILOGUE) {
+#pragma unroll
+      for (int m = 0; m < 8; ++m)
+#pragma unroll
+        for (int n = 0; n < 4; ++n) asm volatile("" ::"v"(acc[m][n]));
+      continue;
+    }
 
     // ---- acc -> v, in place (bits of the float in the int register) ------
 #pragma unroll
