@@ -99,6 +99,10 @@ class FailureMatchRequest(BaseModel):
     # opt out of the routed (approximate) search for this request; a no-op
     # when the service runs exact search anyway
     exact: bool = False
+    # how many matches to return, 1..64 (ops.KWIDE_MAX); absent: the engine's
+    # default (5) and the request served exactly as before the field existed.
+    # More than 8 is always answered by the exact search.
+    top_k: Optional[int] = Field(default=None, ge=1, le=64)
 
 
 class FailureMatch(BaseModel):

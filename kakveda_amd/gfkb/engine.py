@@ -469,9 +469,17 @@ class EmbeddingStore:
         is the index to route through (default: the attached one), for
         callers that snapshot it together with ``valid_n``. ``batched``
         picks the routed scan kernel (``ops.ivf_scan_topk``: None chooses by
-        batch size); it changes no result beyond fp32 summation order."""
+        batch size); it changes no result beyond fp32 summation order.
+
+        ``k > ops.KMAX`` (up to ``ops.KWIDE_MAX`` = 64 on a GPU; more comes
+        back padded) is the wide search, ``ops.cosine_topk_wide`` per segment:
+        always exact and always over the bf16 rows. ``nprobe``, the index and
+        the int8 mirror do not apply to it and it never raises over them; a
+        filtered batch of more than 8 queries is scanned in groups of 8."""
         q = queries.to(self.dtype)
         count = self.count if valid_n is None else min(int(valid_n), self.count)
+        if k > ops.KMAX:
+            return self._search_wide(q, int(k), count, want)
         if nprobe is not None and int(nprobe) < 0:
             raise ValueError("nprobe must be >= 0")
         if nprobe:
@@ -514,6 +522,32 @@ class EmbeddingStore:
             return topk(0, count)
         parts_s, parts_i = [], []
         # the live segments are a prefix of _segments, so labels line up
+        for seg_no, (seg, valid, base) in enumerate(segs):
+            s, i = topk(seg_no, valid)
+            parts_i.append(torch.where(i < 0, i, i + base))
+            parts_s.append(s)
+        all_s = torch.cat(parts_s, dim=1)
+        all_i = torch.cat(parts_i, dim=1)
+        top_s, sel = torch.topk(all_s, min(k, all_s.shape[1]), dim=1)
+        return top_s, all_i.gather(1, sel)
+
+    def _search_wide(
+        self, q: torch.Tensor, k: int, count: int, want: Optional[torch.Tensor]
+    ) -> Tuple[torch.Tensor, torch.Tensor]:
+        """``search`` for k > ops.KMAX: ``ops.cosine_topk_wide`` per live
+        segment and the cross-segment merge of ``search``."""
+        segs = self._live_segments(count)
+        w = None if want is None else want.to(device=self.device, dtype=torch.int32)
+
+        def topk(seg_no: int, n: int):
+            return ops.cosine_topk_wide(
+                q, self._segments[seg_no], k, valid_n=n,
+                labels=None if w is None else self._labels[seg_no], want=w,
+            )
+
+        if len(segs) <= 1:
+            return topk(0, count)
+        parts_s, parts_i = [], []
         for seg_no, (seg, valid, base) in enumerate(segs):
             s, i = topk(seg_no, valid)
             parts_i.append(torch.where(i < 0, i, i + base))

@@ -9,6 +9,10 @@ Kernels (kakveda_amd/ops/hip/):
 - cosine_topk_filtered — the same search with a per-query label predicate
   pushed into the scan (filtered instantiations of the 128x128 list kernel
   and of the streaming small-batch kernel; exact at any selectivity).
+- cosine_topk_wide — the exact search for 8 < k <= 64: a k-deep floor from
+  the prepass partials, the emission kernels of the k <= 8 search, and a
+  block-wide bitonic selection in registers, shuffles and LDS
+  (ops/hip/knn_wide_plan.h, knn_wide_impl.h).
 - quantize_rows_q8 / cosine_topk_q8 — the optional int8 row mirror: per-row
   symmetric int8 codes with the row's scale and an upper bound of its
   quantisation error, and the exact small-batch search that scans the codes
@@ -227,6 +231,105 @@ def cosine_topk_filtered_ref(
         scores = torch.cat([scores, pad_s], dim=1)
         idx = torch.cat([idx, pad_i], dim=1)
     return scores.float(), idx.long()
+
+
+# ---------------------------------------------------------------------------
+# wide exact top-k: KMAX < k <= KWIDE_MAX
+# ---------------------------------------------------------------------------
+
+#: most results per query of ``cosine_topk_wide`` (knn_wide_plan.h KWIDE_MAX)
+KWIDE_MAX = 64
+
+#: batches of ``cosine_topk_wide`` whose candidates overflowed their buffer and
+#: were answered slice by slice instead (a process-wide counter)
+wide_overflow_fallbacks = 0
+
+
+def _wide_ext():
+    ext = _require_ext()
+    if int(ext.KWIDE_MAX) != KWIDE_MAX:
+        raise RuntimeError(
+            f"ops.KWIDE_MAX = {KWIDE_MAX} but the built extension has "
+            f"KWIDE_MAX = {int(ext.KWIDE_MAX)}: rebuild it"
+        )
+    return ext
+
+
+def cosine_topk_wide(
+    queries: torch.Tensor,
+    corpus: torch.Tensor,
+    k: int,
+    valid_n: Optional[int] = None,
+    labels: Optional[torch.Tensor] = None,
+    want: Optional[torch.Tensor] = None,
+    cap: Optional[int] = None,
+    seg: Optional[int] = None,
+) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Exact top-k for k up to ``KWIDE_MAX`` = 64: ``cosine_topk`` (or, with
+    ``labels``/``want``, ``cosine_topk_filtered``) without the KMAX clamp.
+
+    Returns (scores f32 [B, k], idx i64 [B, k]), score descending (on a GPU,
+    among equal scores, index ascending); ranks past the eligible rows are
+    (-inf, -1). On a GPU ``k <= KMAX`` is answered by ``cosine_topk`` /
+    ``cosine_topk_filtered`` as they are, and ``k > KWIDE_MAX`` returns the top
+    ``KWIDE_MAX`` padded, the convention of ``cosine_topk``. On a CPU it is the
+    plain-torch reference at any k.
+
+    The GPU path (ops/hip/knn_wide_plan.h) takes per query the k-th largest
+    partial of an 8-deep prepass over a prefix of the corpus as a floor, emits
+    every row at or above it with the kernels of the k <= 8 search, and selects
+    the top k of those in LDS. It scans the whole corpus once for B <= 8
+    (streaming kernel) and for unfiltered batches (8-phase MFMA kernel); a
+    filtered batch of more than 8 queries, and any batch over fewer than 4,096
+    rows, is served in groups of 8 queries, each group reading the corpus
+    again. Unit rows are the precondition, as for ``cosine_topk``.
+
+    ``cap`` (candidates per query; default KAKVEDA_KNN_EMIT_CAP, 32,768) and
+    ``seg`` (records per block segment of the 8-phase launch) are for tests and
+    measurements. A batch that overflows either is answered exactly over
+    consecutive corpus slices of ``cap`` rows and counted in
+    ``wide_overflow_fallbacks``.
+    """
+    global wide_overflow_fallbacks
+    if (labels is None) != (want is None):
+        raise ValueError("labels and want go together")
+    n = int(valid_n) if valid_n is not None else corpus.shape[0]
+    B = queries.shape[0]
+    k = int(k)
+    if n <= 0 or B == 0:
+        return (
+            torch.full((B, k), float("-inf"), dtype=torch.float32, device=queries.device),
+            torch.full((B, k), -1, dtype=torch.int64, device=queries.device),
+        )
+    if queries.device.type != "cuda":
+        if labels is None:
+            return cosine_topk_ref(queries, corpus, k, n)
+        return cosine_topk_filtered_ref(queries, corpus, labels, want, k, n)
+    if k <= KMAX:
+        if labels is None:
+            return cosine_topk(queries, corpus, k, n)
+        return cosine_topk_filtered(queries, corpus, labels, want, k, n)
+    ext = _wide_ext()
+    kk = min(k, KWIDE_MAX)
+    scores, idx, fallback = ext.cosine_topk_wide(
+        queries,
+        corpus,
+        kk,
+        n,
+        None if labels is None else labels.to(device=corpus.device, dtype=torch.int32).contiguous(),
+        None if want is None else want.to(device=queries.device, dtype=torch.int32).contiguous(),
+        int(cap or 0),
+        int(seg or 0),
+    )
+    wide_overflow_fallbacks += int(fallback == 1)
+    # one sentinel out, as cosine_topk_filtered
+    scores = torch.where(idx < 0, torch.full_like(scores, float("-inf")), scores)
+    if kk < k:
+        pad_s = torch.full((B, k - kk), float("-inf"), dtype=scores.dtype, device=scores.device)
+        pad_i = torch.full((B, k - kk), -1, dtype=idx.dtype, device=idx.device)
+        scores = torch.cat([scores, pad_s], dim=1)
+        idx = torch.cat([idx, pad_i], dim=1)
+    return scores, idx
 
 
 # ---------------------------------------------------------------------------

@@ -12,6 +12,7 @@
 #include "featurize_impl.h"
 #include "q8_impl.h"
 #include "q8_screen_impl.h"
+#include "knn_wide_impl.h"
 
 using namespace kakveda;
 
@@ -399,6 +400,198 @@ std::tuple<torch::Tensor, torch::Tensor> cosine_topk_filtered(
   static const KnnEnv env = parse_knn_env(std::getenv);
   return cosine_topk_impl(queries, corpus, (int)k, N, env, true,
                           Filter{labels.data_ptr<int>(), want.data_ptr<int>()});
+}
+
+// ---------------------------------------------------------------------------
+// Wide exact search, KMAX < k <= KWIDE_MAX (knn_wide_plan.h, knn_wide_impl.h)
+// ---------------------------------------------------------------------------
+namespace {
+
+struct WidePass {
+  torch::Tensor cand, ccount;  // i64 [B, cap], i32 [B]
+};
+
+// Floors and emission of one pass over the a.N corpus rows at a.c: afterwards
+// cand / ccount hold, per query, every eligible row scoring at least the
+// query's wide floor (every eligible row where it has none).
+WidePass run_wide_pass(const KnnArgs& a, const WidePlan& p, Filter flt) {
+  // A fresh threshold array that only ever holds the wide floor: the prepass
+  // below gets none (its 8-deep list minima bound the 8th best, not the k-th).
+  auto rowthr = new_rowthr(a);
+  unsigned* const thr = (unsigned*)rowthr.data_ptr<int>();
+  if (p.prepass) {
+    const long entries = (long)p.pre_grid * KMAX;
+    auto ppre_s = torch::empty({(long)a.B * entries}, a.f32());
+    auto ppre_i = torch::empty({(long)a.B * entries}, a.i32());
+    launch_partial128(11, dim3(p.pre_grid, (a.B + BM - 1) / BM), a,
+                      ppre_s.data_ptr<float>(), ppre_i.data_ptr<int>(),
+                      p.pre_tiles, p.pre_grid, nullptr, flt);
+    hipLaunchKernelGGL(wide_floor_kernel, dim3(a.B), dim3(WSEL_THREADS), 0,
+                       a.stream, (const float*)ppre_s.data_ptr<float>(),
+                       (const int*)ppre_i.data_ptr<int>(), (int)entries, p.k, thr);
+  }
+  WidePass w{torch::empty({(long)a.B, p.cap}, a.i64()),
+             torch::zeros({(long)a.B}, a.i32())};
+  unsigned long long* const cand = (unsigned long long*)w.cand.data_ptr<int64_t>();
+  unsigned* const ccount = (unsigned*)w.ccount.data_ptr<int>();
+  if (p.main == WideMain::Emit8p) {
+    EmitBufs e{w.cand, w.ccount, {}, {}};
+    const long blocks = (long)p.ch.nchunks * p.ch.row_tiles;
+    e.eseg = torch::empty({blocks, p.seg}, a.i64());
+    e.esegcnt = torch::empty({blocks}, a.i32());
+    auto pscore = torch::empty({(long)a.B * p.ch.nchunks * KMAX}, a.f32());
+    auto pidx = torch::empty({(long)a.B * p.ch.nchunks * KMAX}, a.i32());
+    launch_emit8p(9, a, p.ch, pscore, pidx, rowthr, e, p.cap, p.seg);
+    return w;
+  }
+  const auto kernel = flt ? smallb_emit_kernel_v4<true> : smallb_emit_kernel_v4<false>;
+  for (int g = 0; g < p.groups; ++g) {
+    const WideSpan s = wide_group(a.B, g);
+    hipLaunchKernelGGL(kernel, dim3(p.smallb_blocks), dim3(256),
+                       (size_t)s.count * a.D * 2, a.stream, a.q + s.first * a.D,
+                       a.c, (int)s.count, (long)a.N, a.D,
+                       (const unsigned*)thr + s.first, cand + s.first * p.cap,
+                       ccount + s.first, p.cap, flt.labels,
+                       flt ? flt.want + s.first : nullptr);
+  }
+  return w;
+}
+
+struct WideResult {
+  torch::Tensor scores, idx, counts;
+  int64_t fallback;
+};
+
+WideResult cosine_topk_wide_impl(const torch::Tensor& queries,
+                                 const torch::Tensor& corpus, int64_t k,
+                                 int64_t valid_n,
+                                 const c10::optional<torch::Tensor>& labels,
+                                 const c10::optional<torch::Tensor>& want,
+                                 int64_t cap, int64_t seg) {
+  check_bf16_2d(queries, "queries");
+  check_bf16_2d(corpus, "corpus");
+  const int D = queries.size(1);
+  const int N = (int)valid_n;
+  TORCH_CHECK(corpus.size(1) == D, "dim mismatch");
+  TORCH_CHECK(valid_n >= 1 && valid_n <= corpus.size(0) && valid_n <= 0x7fffffffL,
+              "valid_n out of range");
+  TORCH_CHECK(D % BK == 0, "D must be a multiple of ", BK);
+  TORCH_CHECK(k >= 1 && k <= KWIDE_MAX, "k must be in [1,", KWIDE_MAX, "]");
+  TORCH_CHECK(cap >= 0 && cap <= (1L << 24) && seg >= 0, "cap or seg out of range");
+  TORCH_CHECK((size_t)WIDE_GROUP * D * 2 <= 64 * 1024, "cosine_topk_wide: ",
+              WIDE_GROUP, " queries of D = ", D,
+              " do not fit the streaming kernel's 64 KiB of LDS");
+  TORCH_CHECK(queries.size(0) >= 1 &&
+                  (queries.size(0) + BM - 1) / BM <= MAX_GRID_Y,
+              "cosine_topk_wide: split the batch");
+  TORCH_CHECK(labels.has_value() == want.has_value(), "labels and want go together");
+  Filter flt;
+  if (labels) {
+    const torch::Tensor& l = *labels;
+    const torch::Tensor& w = *want;
+    TORCH_CHECK(l.is_cuda() && l.device() == corpus.device() &&
+                    l.scalar_type() == torch::kInt32 && l.dim() == 1 &&
+                    l.is_contiguous() && l.size(0) >= N,
+                "labels must be contiguous 1-D i32 on the corpus device with at "
+                "least valid_n entries");
+    TORCH_CHECK(w.is_cuda() && w.device() == queries.device() &&
+                    w.scalar_type() == torch::kInt32 && w.dim() == 1 &&
+                    w.is_contiguous() && w.size(0) == queries.size(0),
+                "want must be contiguous 1-D i32 on the query device with one "
+                "entry per query row");
+    flt = Filter{l.data_ptr<int>(), w.data_ptr<int>()};
+  }
+  static const KnnEnv env = parse_knn_env(std::getenv);
+  const KnnArgs a = knn_args(queries, corpus, N);
+  const long ccap = cap > 0 ? cap : std::max(1L, env.cap);
+  const WidePlan p = plan_wide(a.B, N, k, (bool)flt, ccap, seg > 0 ? seg : env.seg,
+                               env.target, false);
+  const int kk = p.k;
+  WidePass w = run_wide_pass(a, p, flt);
+  auto out_score = torch::empty({(long)a.B, (long)kk}, a.f32());
+  auto out_idx = torch::empty({(long)a.B, (long)kk}, a.i64());
+  hipLaunchKernelGGL(emit_merge_topk_wide<false>, dim3(a.B), dim3(WSEL_THREADS), 0,
+                     a.stream, (const unsigned long long*)w.cand.data_ptr<int64_t>(),
+                     (const unsigned*)w.ccount.data_ptr<int>(), p.cap, 0u, kk,
+                     out_score.data_ptr<float>(), (long*)out_idx.data_ptr<int64_t>(),
+                     (unsigned long long*)nullptr, 0L, 0L, 0u);
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+  // the one readback: a count past cap is a row that lost candidates or a
+  // poisoned record segment (emit_bin)
+  const long mx = (long)w.ccount.max().item<int>();
+  if (env.emit_debug)
+    printf("wide: rows=%d k=%d max=%ld mean=%.1f cap=%ld seg=%ld main=%d%s\n", a.B,
+           kk, mx, w.ccount.to(torch::kFloat32).mean().item<float>(), p.cap, p.seg,
+           (int)p.main, mx > p.cap ? "  FALLBACK" : "");
+  if (mx <= p.cap) return {out_score, out_idx, w.ccount, 0};
+
+  static bool warned = false;
+  if (!warned) {
+    warned = true;
+    fprintf(stderr,
+            "[kakveda] wide top-k candidate overflow (max=%ld > cap=%ld): "
+            "answering this batch over corpus slices of %ld rows\n",
+            mx, p.cap, p.cap);
+  }
+  // Sliced fallback: each slice of at most cap rows through the same
+  // pipeline (streaming kernel: no segments, at most its rows emitted), its
+  // top k kept as packed words with corpus-wide columns; then one selection
+  // across the slices.
+  const long slices = wide_slice_count(N, p.cap);
+  auto packed = torch::empty({(long)a.B, slices * kk}, a.i64());
+  for (long s = 0; s < slices; ++s) {
+    const WideSpan sl = wide_slice(N, p.cap, s);
+    KnnArgs as = a;
+    as.c = a.c + sl.first * (long)D;
+    as.N = (int)sl.count;
+    Filter fs = flt;
+    if (fs) fs.labels = flt.labels + sl.first;
+    const WidePlan ps =
+        plan_wide(a.B, as.N, kk, (bool)flt, p.cap, 0, env.target, true);
+    WidePass ws = run_wide_pass(as, ps, fs);
+    hipLaunchKernelGGL(emit_merge_topk_wide<true>, dim3(a.B), dim3(WSEL_THREADS), 0,
+                       a.stream,
+                       (const unsigned long long*)ws.cand.data_ptr<int64_t>(),
+                       (const unsigned*)ws.ccount.data_ptr<int>(), p.cap, 0u, kk,
+                       (float*)nullptr, (long*)nullptr,
+                       (unsigned long long*)packed.data_ptr<int64_t>(), slices * kk,
+                       s * kk, (unsigned)sl.first);
+  }
+  hipLaunchKernelGGL(emit_merge_topk_wide<false>, dim3(a.B), dim3(WSEL_THREADS), 0,
+                     a.stream, (const unsigned long long*)packed.data_ptr<int64_t>(),
+                     (const unsigned*)nullptr, slices * kk, (unsigned)(slices * kk),
+                     kk, out_score.data_ptr<float>(),
+                     (long*)out_idx.data_ptr<int64_t>(),
+                     (unsigned long long*)nullptr, 0L, 0L, 0u);
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+  return {out_score, out_idx, w.ccount, 1};
+}
+
+}  // namespace
+
+// Exact top-k for k up to KWIDE_MAX: (scores f32 [B, k], idx i64 [B, k],
+// fallback). labels / want restrict it as cosine_topk_filtered does. cap > 0
+// overrides the candidates per query (KAKVEDA_KNN_EMIT_CAP otherwise), seg > 0
+// the records per block segment of the 8-phase launch. fallback is 1 when the
+// candidates overflowed and the batch was answered slice by slice.
+std::tuple<torch::Tensor, torch::Tensor, int64_t> cosine_topk_wide(
+    torch::Tensor queries, torch::Tensor corpus, int64_t k, int64_t valid_n,
+    c10::optional<torch::Tensor> labels, c10::optional<torch::Tensor> want,
+    int64_t cap, int64_t seg) {
+  WideResult r =
+      cosine_topk_wide_impl(queries, corpus, k, valid_n, labels, want, cap, seg);
+  return {r.scores, r.idx, r.fallback};
+}
+
+// Benchmark probe: the same request, returning the candidates per query of
+// its first pass as well: (scores, idx, fallback, counts i32 [B]).
+std::tuple<torch::Tensor, torch::Tensor, int64_t, torch::Tensor> wide_counts_probe(
+    torch::Tensor queries, torch::Tensor corpus, int64_t k, int64_t valid_n,
+    c10::optional<torch::Tensor> labels, c10::optional<torch::Tensor> want,
+    int64_t cap, int64_t seg) {
+  WideResult r =
+      cosine_topk_wide_impl(queries, corpus, k, valid_n, labels, want, cap, seg);
+  return {r.scores, r.idx, r.fallback, r.counts};
 }
 
 // ---------------------------------------------------------------------------
@@ -1592,6 +1785,19 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("cnorm") = pybind11::none(),
         pybind11::arg("batch_min_b") = (int64_t)0,
         pybind11::arg("cap") = (int64_t)0, pybind11::arg("stages") = (int64_t)0);
+  m.def("cosine_topk_wide", &cosine_topk_wide,
+        "exact top-k for KMAX < k <= KWIDE_MAX: floors, emission, wide selection",
+        pybind11::arg("queries"), pybind11::arg("corpus"), pybind11::arg("k"),
+        pybind11::arg("valid_n"), pybind11::arg("labels") = pybind11::none(),
+        pybind11::arg("want") = pybind11::none(),
+        pybind11::arg("cap") = (int64_t)0, pybind11::arg("seg") = (int64_t)0);
+  m.def("wide_counts_probe", &wide_counts_probe,
+        "cosine_topk_wide plus the candidates per query of its first pass",
+        pybind11::arg("queries"), pybind11::arg("corpus"), pybind11::arg("k"),
+        pybind11::arg("valid_n"), pybind11::arg("labels") = pybind11::none(),
+        pybind11::arg("want") = pybind11::none(),
+        pybind11::arg("cap") = (int64_t)0, pybind11::arg("seg") = (int64_t)0);
+  m.attr("KWIDE_MAX") = KWIDE_MAX;
   m.def("q8_stage_plan", &q8_stage_plan_op,
         "stage plan of the batched int8 screen: tile bounds and chunkings",
         pybind11::arg("B"), pybind11::arg("N"), pybind11::arg("k"),

@@ -64,6 +64,7 @@ class MatchBatcher:
         failure_type: Optional[str] = None,
         filter_first: bool = False,
         exact: bool = False,
+        top_k: Optional[int] = None,
     ):
         self._ensure_thread()
         item: Dict[str, Any] = {
@@ -71,6 +72,7 @@ class MatchBatcher:
             "ftype": failure_type,
             "first": filter_first,
             "exact": exact,
+            "top_k": top_k,
             "ev": threading.Event(),
             "res": None,
             "err": None,
@@ -90,29 +92,61 @@ class MatchBatcher:
                     batch.append(self._q.get_nowait())
                 except queue.Empty:
                     break
-            try:
-                first = [b["first"] for b in batch]
-                # an all-unset batch makes the call it always made
-                extra = {"filter_first": first} if any(first) else {}
-                # one request asking for exact makes its whole batch exact.
-                # A routed batch needs no cap on its size: from
-                # ops.IVF_BATCHED_MIN_B queries on the store takes the
-                # list-major scan, which gathers a probed list once per 16
-                # queries and stays below the exact search's time
-                if any(b["exact"] for b in batch):
-                    extra["nprobe"] = 0
-                results = self.engine.match_batch(
-                    [b["text"] for b in batch], [b["ftype"] for b in batch], **extra
-                )
-                for b, r in zip(batch, results):
-                    b["res"] = r
-            except Exception as exc:  # surfaced to every waiting request
-                for b in batch:
-                    b["err"] = exc
-            self.batches += 1
+            # At most two engine calls per batch: the requests without a
+            # top_k go in exactly the call made before the field existed,
+            # those with one in a second call at their largest top_k.
+            plain = [b for b in batch if b.get("top_k") is None]
+            asked = [b for b in batch if b.get("top_k") is not None]
+            for group, run in ((plain, self._run_plain), (asked, self._run_top_k)):
+                if not group:
+                    continue
+                try:
+                    run(group)
+                except Exception as exc:  # surfaced to every waiting request
+                    for b in group:
+                        b["err"] = exc
+                self.batches += 1
             self.requests += len(batch)
             for b in batch:
                 b["ev"].set()
+
+    def _extra(self, batch) -> Dict[str, Any]:
+        first = [b["first"] for b in batch]
+        # an all-unset batch makes the call it always made
+        extra: Dict[str, Any] = {"filter_first": first} if any(first) else {}
+        # one request asking for exact makes its whole batch exact.
+        # A routed batch needs no cap on its size: from
+        # ops.IVF_BATCHED_MIN_B queries on the store takes the
+        # list-major scan, which gathers a probed list once per 16
+        # queries and stays below the exact search's time
+        if any(b["exact"] for b in batch):
+            extra["nprobe"] = 0
+        return extra
+
+    def _run_plain(self, batch) -> None:
+        results = self.engine.match_batch(
+            [b["text"] for b in batch], [b["ftype"] for b in batch], **self._extra(batch)
+        )
+        for b, r in zip(batch, results):
+            b["res"] = r
+
+    def _run_top_k(self, batch) -> None:
+        """One call at the largest top_k of the group; each result is cut to
+        its own. The reference's order holds per request: cut to top_k first,
+        then drop other types. So only a filter-first request hands its type
+        to the engine (the type is then applied inside the search, and the
+        best top_k of that type are a prefix of the best of the call); every
+        other request is searched untyped and filtered here, after its cut."""
+        k = max(int(b["top_k"]) for b in batch)
+        types = [b["ftype"] if b["first"] else None for b in batch]
+        results = self.engine.match_batch(
+            [b["text"] for b in batch], types, top_k=k, **self._extra(batch)
+        )
+        for b, r in zip(batch, results):
+            r = r[: int(b["top_k"])]
+            if b["ftype"] and not b["first"]:
+                r = [m for m in r if m.failure_type == b["ftype"]]
+            b["res"] = r
 
 
 class UpsertFailureRequest(BaseModel):
@@ -252,9 +286,12 @@ def create_app(
                 failure_type=req.failure_type,
                 filter_first=req.filter_first,
                 exact=req.exact,
+                **({} if req.top_k is None else {"top_k": req.top_k}),
             )
         else:
             extra = {"nprobe": 0} if req.exact else {}
+            if req.top_k is not None:
+                extra["top_k"] = req.top_k
             matches = engine.match(
                 req.signature_text,
                 failure_type=req.failure_type,
